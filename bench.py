@@ -7,15 +7,19 @@ in fp32 arithmetic (split-fp32 MFMA: every fp32 operand as the exact sum of thre
 plane products per fp32 product accumulated in fp32, deterministic reductions: the mode the golden
 parity tests pin; --fp32-mfma exact runs the convs on the fp32 MFMA instead).  One "step" = ``MoEWrapper.train_step`` (router, G fwd x2 + bwd x2, D fwd
 x4 + bwd x4, aux regressor fwd/bwd, losses, four fused Adam updates; with N > 1 also the RCCL
-gradient all-reduces, SyncBN by default).  Beside the headline it measures the bf16 performance
-mode (bf16 GEMM operands, fp32 accumulation) as ``perf_bf16``.
+gradient all-reduces, SyncBN by default).
 
     python bench.py [--gpus N --steps K --warmup W --batch B --experts E --arch neutron|proton]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-Prints ONE JSON line (rank 0) with the metric, a live-measured roofline of the dominant kernel
-(HIP events on its launch stream inside eager steps of the same model) and the CPU baseline (the
-oracle, a CPU fp32 restatement of the same step, timed on this host's cores on a bounded sample).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the metric.
+``--dump-outputs DIR`` also writes what the last timed step produced (its metric scalars and the
+model state it left) as ``DIR/<name>.npy``; the inputs and seeds are fixed, so two builds can be
+compared array for array.  ``--full`` adds the legs that take runs of their own: a live-measured
+roofline of the dominant kernel (HIP events on its launch stream inside eager steps of the same
+model), the bf16 performance mode (bf16 GEMM operands, fp32 accumulation) as ``perf_bf16`` and the
+CPU baseline (the oracle, a CPU fp32 restatement of the same step, timed on this host's cores on a
+bounded sample); ``--no-probe``, ``--other-steps 0`` and ``--no-cpu-baseline`` drop single legs of it.
 """
 from __future__ import annotations
 
@@ -185,26 +189,58 @@ def timed(step, steps, world):
         dist.barrier()
     torch.cuda.synchronize()
     evs = [torch.cuda.Event() for _ in range(MAX_INFLIGHT)]
+    last = None
     t0 = time.perf_counter()
     for i in range(steps):
         if i >= MAX_INFLIGHT:
             evs[i % MAX_INFLIGHT].synchronize()
-        step()
+        last = step()
         evs[i % MAX_INFLIGHT].record()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, last
 
 
 def make_step(moe, step_args, use_graph):
+    """The timed step: returns the step's metric dict (device scalars), as train_step does."""
     def eager_step():
-        moe.train_step(*step_args)
+        return moe.train_step(*step_args)
     if not use_graph:
         return eager_step, None
     from expertsim.graph import StepGraph
     sg = StepGraph(moe, step_args, warmup=1, allow_dp=True)
     return sg.replay, sg
+
+
+# --dump-outputs: at most this many bytes in all (float32 / float64 elements; larger arrays are sampled)
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(path, metrics, moe):
+    """What a caller of the timed step holds after its last step: the metric dict it returned
+    (``metric.<key>.npy``, float32 scalars) and the model state it left behind (``state.<key>.npy``:
+    every state_dict tensor of the generators, discriminators, aux regressors and router; floating
+    tensors as float32, integer ones as float64).  An array above the per-array limit that keeps the
+    whole dump within DUMP_BUDGET_BYTES is stored as a fixed seeded sample of its flattened elements."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {f"metric.{k}": v for k, v in metrics.items()}
+    arrays.update({f"state.{k}": v for k, v in moe.state_dict().items() if torch.is_tensor(v)})
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        host[k] = (v.float() if v.is_floating_point() else v.double()).cpu().numpy()
+    budget = DUMP_BUDGET_BYTES // 8          # elements, each charged as a float64
+    limit = budget
+    while sum(min(a.size, limit) for a in host.values()) > budget:
+        limit = limit * 3 // 4
+    for k, a in host.items():
+        if a.size > limit:
+            ix = np.sort(np.random.default_rng(0).integers(0, a.size, size=limit))
+            a = a.reshape(-1)[ix]
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def exec_flops(reset=False):
@@ -357,8 +393,9 @@ def step_exec_frac(roof, ms_per_step):
     return round(t / (ms_per_step * 1e-3), 4)
 
 
-def run_mode(args, precision, steps, warmup, dev, rank, world, ddp, probe_steps):
-    """Build a model in ``precision``, warm up, time ``steps`` steps; returns (value, dt, roof, launch)."""
+def run_mode(args, precision, steps, warmup, dev, rank, world, ddp, probe_steps, dump_dir=None):
+    """Build a model in ``precision``, warm up, time ``steps`` steps; returns (value, dt, roof, launch).
+    dump_dir: rank 0 writes the last timed step's outputs there (dump_outputs)."""
     import torch
     import torch.distributed as dist
     from expertsim.train.ddp import DataParallel
@@ -380,9 +417,12 @@ def run_mode(args, precision, steps, warmup, dev, rank, world, ddp, probe_steps)
     for _ in range(warmup):
         eager()
     step, sg = make_step(moe, step_args, use_graph)
-    dt = timed(step, steps, world)
+    dt, last = timed(step, steps, world)
     if sg is not None:
         sg.sync_host_state([*og, *od, *oa, orr])
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, last, moe)
+    del last
     # the probe's eager steps run without the captured graphs: release their pools first
     del step, sg
     step = sg = None
@@ -419,12 +459,17 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"],
                     help="headline: fp32 = the reference's precision (split-fp32 or exact fp32 MFMA, the mode "
                          "the golden parity tests pin); bf16 = bf16 GEMM operands, fp32 accumulation")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-kernel roofline probe, the other "
+                         "precision's secondary line and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (metric scalars, model state) as DIR/<name>.npy")
     ap.add_argument("--other-steps", type=int, default=50,
-                    help="timed steps of the other precision's secondary line (0: skip)")
+                    help="--full: timed steps of the other precision's secondary line (0: skip)")
     ap.add_argument("--fp32-mfma", choices=["exact", "split"], default="split",
                     help="fp32 conv arithmetic: exact fp32 MFMA, or split-fp32 (three bf16 planes, six products)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the per-kernel HIP-event probe")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-probe", action="store_true", help="--full: skip the per-kernel HIP-event probe")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the step as a captured HIP graph (auto: single process)")
     ap.add_argument("--sync-bn", action="store_true",
@@ -438,6 +483,8 @@ def main():
                     help="process-group backend (nccl = RCCL over xGMI; gloo only to rehearse several ranks "
                          "on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # measured lines come from the default build and kernel paths only: no ES_* environment override
     # (ES_LIB would load another build; INTEGRATION.md §2 lists the test hooks)
     stray = sorted(k for k in os.environ if k.startswith("ES_"))
@@ -473,12 +520,12 @@ def main():
 
     # E > 1: the probe runs eager steps (the experts' ops visible to the host) and scales each expert's
     # work by its routed share of the batch (dynamic rows)
-    probe_steps = 0 if args.no_probe else 5
+    probe_steps = 5 if args.full and not args.no_probe else 0
     value, dt, roof, launch = run_mode(args, args.precision, args.steps, args.warmup, dev, rank, world, ddp,
-                                       probe_steps)
+                                       probe_steps, args.dump_outputs)
     other = None
     other_p = "bf16" if args.precision == "fp32" else "fp32"
-    if args.other_steps > 0 and world == 1:
+    if args.full and args.other_steps > 0 and world == 1:
         vo, dto, roofo, launcho = run_mode(args, other_p, args.other_steps, 5, dev, rank, world, ddp,
                                            3 if probe_steps else 0)
         other = {"dtype": other_p, "value": round(vo, 2), "unit": "images/s", "steps": args.other_steps,
@@ -528,7 +575,7 @@ def main():
             out["precision_note"] = "bf16 GEMM operands, fp32 accumulation"
         if other is not None:
             out["perf_bf16" if other_p == "bf16" else "parity_fp32"] = other
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.arch)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if ddp:

@@ -34,6 +34,34 @@ def test_aggregate_expert_ops_scales_by_routed_share():
     assert s["alg_per_op"] == pytest.approx(per * B * (2 * 0.75 + 2 * 0.25) / 4)
 
 
+def test_dump_outputs_names_dtypes_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: metric scalars and state tensors as float32 (integer state as float64), whole
+    when they fit; above the budget an array is the same seeded sample of its elements every time."""
+    import numpy as np
+    import torch
+    import bench
+    m = torch.nn.Sequential(torch.nn.Linear(40, 50), torch.nn.BatchNorm1d(50))
+    metrics = {"gen_loss": torch.tensor(1.5), "disc_loss": torch.tensor(-0.25)}
+    bench.dump_outputs(str(tmp_path / "a"), metrics, m)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"metric.gen_loss", "metric.disc_loss"} | {f"state.{k}" for k in m.state_dict()}
+    assert got["metric.gen_loss"].dtype == np.float32 and got["metric.gen_loss"] == np.float32(1.5)
+    assert got["state.0.weight"].dtype == np.float32
+    assert np.array_equal(got["state.0.weight"], m[0].weight.detach().numpy())
+    assert got["state.1.num_batches_tracked"].dtype == np.float64
+    # 2000 weights against a budget of 1000 elements: the large array is sampled, the small ones whole
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 1000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), metrics, m)
+    b = {f.stem: np.load(f) for f in (tmp_path / "b").glob("*.npy")}
+    assert set(b) == set(got) and sum(a.size for a in b.values()) <= 1000
+    assert b["state.0.weight"].ndim == 1 and 0 < b["state.0.weight"].size < 2000
+    assert np.isin(b["state.0.weight"], got["state.0.weight"]).all()
+    assert np.array_equal(b["state.0.bias"], got["state.0.bias"])
+    for k, a in b.items():
+        assert np.array_equal(a, np.load(tmp_path / "c" / (k + ".npy"))), k
+
+
 def test_aggregate_expert_ops_empty_expert():
     """An expert routed no sample contributes its time but no work."""
     import bench

@@ -4,7 +4,7 @@
 # included -- and summed vs interval-union kernel time.)
 set -o pipefail
 tag=$1; shift
-[ $# -eq 0 ] && set -- --steps 20 --warmup 3 --other-steps 0 --no-cpu-baseline
+[ $# -eq 0 ] && set -- --full --steps 20 --warmup 3 --other-steps 0 --no-cpu-baseline
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/benchprof_$tag
 mkdir -p $O

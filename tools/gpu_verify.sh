@@ -9,4 +9,4 @@ rc=$?
 echo "pytest rc=$rc" >> $O/t_$TAG.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_$TAG.log 2>&1 && \
-timeout -k 10 400 python bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+timeout -k 10 400 python bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err
