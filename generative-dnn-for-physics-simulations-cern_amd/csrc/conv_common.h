@@ -79,6 +79,11 @@ struct ConvArgs {
   int prio;                     // split-fp32 ring kernels: waves 4-7 at s_setprio 1 (VALU arbitration)
   int nbase;                    // dynamic rows: the launch's first image within d.rows' count (chunks)
   int mslot;                    // generic kernels (device-side): the launch's M, the split partials' stride
+  // FWD with a per-output-channel affine + activation epilogue (es_conv2d_fwd_affine: an eval-mode
+  // BatchNorm folded by es_bn_fold, then LeakyReLU / ReLU): read only by the AFF instantiations
+  const float *epi_scale, *epi_shift;
+  int epi_act;
+  float epi_slope;
 };
 
 // Images of the launch that carry data: d.N, or with dynamic rows (es_conv_desc_t.rows, a device
@@ -140,6 +145,20 @@ struct StatsRequest {
   int chunks;
 };
 extern thread_local StatsRequest g_stats_req;
+
+// es_conv2d_fwd_affine: the caller's request (host, per thread); a ring FWD launch whose kernel
+// applies y = act(scale[k] * (acc + bias[k]) + shift[k]) before rounding sets fused.  Such a request
+// never comes with a StatsRequest.
+struct AffineRequest {
+  const float* scale;
+  const float* shift;
+  int act;
+  float slope;
+  int fused;
+};
+extern thread_local AffineRequest g_aff_req;
+// the fp32 MFMA arithmetic level of the ring kernels (es_conv_set_f32_split: 0 exact, 1 / 2 split-fp32)
+int es_f32_split_level();
 
 // which ring path the last conv launch took (host, per thread; es_conv_exec_flops accounting):
 // bit 0 a ring kernel ran, bit 1 split-fp32 planes, bit 2 the sub-pixel decomposition

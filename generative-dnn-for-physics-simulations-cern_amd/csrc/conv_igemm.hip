@@ -869,8 +869,11 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
     const int nch = MODE == MODE_FWD ? a.d.C : a.d.K;
     const int tiles = ((a.M + 127) / 128) * ((a.Ng + 127) / 128);
     const bool splitk_better = a.dense_f32_out && tiles < 256 && a.Kd / 64 >= 16;   // see below
-    if (avec && bvec && nch % 64 == 0 && a.d.stride <= 2 && a.d.hmap == nullptr && a.M >= 128 && !splitk_better &&
-        !g_no_glds) {
+    // (an affine-epilogue FWD, es_conv2d_fwd_affine, also takes the ring below 128 rows: its tiles pad
+    // the rows, and only the ring kernels carry that epilogue)
+    const bool small_aff = MODE == MODE_FWD && a.M < 128 && g_aff_req.scale != nullptr;
+    if (avec && bvec && nch % 64 == 0 && a.d.stride <= 2 && a.d.hmap == nullptr && (a.M >= 128 || small_aff) &&
+        !splitk_better && !g_no_glds) {
       a.k_per_split = a.Kd;
       a.splitk = 0;
       if (a.Kd % 64 == 0) {
@@ -880,8 +883,10 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
           return ES_OK;
         }
       }
-      if (a.Ng > 64) return launch_glds<MODE, 128, 128>(a, st);
-      return launch_glds<MODE, 128, 64>(a, st);
+      if (!small_aff) {
+        if (a.Ng > 64) return launch_glds<MODE, 128, 128>(a, st);
+        return launch_glds<MODE, 128, 64>(a, st);
+      }
     }
   }
   if constexpr (sizeof(T) == 4 && MODE != MODE_WGRAD) {
@@ -891,8 +896,9 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
     // (the gathered grid's pixels per image: >= 8 keeps the row tiles' padding small; the aux
     // regressor's conv4 has a 1 x 15 output and a 3 x 17 input; linears take the pixel view)
     const int gpix = MODE == MODE_FWD ? a.d.P * a.d.Q : a.d.Hu * a.d.Wu;
+    const bool small_aff = MODE == MODE_FWD && a.M < 128 && g_aff_req.scale != nullptr && es_f32_split_level() > 0;
     if (avec && bvec && nch % 32 == 0 && a.Kd % 32 == 0 && a.d.stride <= 2 && a.d.hmap == nullptr &&
-        gpix >= 8 && a.M >= 128 && !g_no_glds) {
+        gpix >= 8 && (a.M >= 128 || small_aff) && !g_no_glds) {
       a.k_per_split = a.Kd;
       a.splitk = 0;
       const int rc = es_conv_ring_launch_f32(a, MODE, st);
@@ -1120,6 +1126,22 @@ extern "C" int es_conv2d_fwd_stats(const es_conv_desc_t* d, es_dtype_t dt, const
   const int rc = es_conv2d_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, stream);
   *chunks = g_stats_req.chunks;
   g_stats_req = StatsRequest{nullptr, 0, 0};
+  return rc;
+}
+
+// es_conv2d_fwd with y = act(scale[k] * (acc + bias[k]) + shift[k]) applied before the rounding, when
+// the kernel that runs the conv carries that epilogue (the ring FWD kernels of conv_mfma.hip in bf16
+// and split-fp32); otherwise y is es_conv2d_fwd's and *fused = 0.
+extern "C" int es_conv2d_fwd_affine(const es_conv_desc_t* d, es_dtype_t dt, const void* x, const int64_t xs[4],
+                                    const void* wk, const float* bias, const es_affine_t* epi, void* y,
+                                    es_dtype_t ydt, const int64_t ys[4], int* fused, es_stream_t stream) {
+  ES_CHECK_ARG(epi && epi->scale && epi->shift && fused, "conv fwd affine: epi / scale / shift / fused NULL");
+  ES_CHECK_ARG(epi->act == ES_ACT_NONE || epi->act == ES_ACT_RELU || epi->act == ES_ACT_LRELU,
+               "conv fwd affine: unknown activation %d", epi->act);
+  g_aff_req = AffineRequest{epi->scale, epi->shift, epi->act, epi->slope, 0};
+  const int rc = es_conv2d_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, stream);
+  *fused = rc == ES_OK ? g_aff_req.fused : 0;
+  g_aff_req = AffineRequest{nullptr, nullptr, 0, 0.f, 0};
   return rc;
 }
 

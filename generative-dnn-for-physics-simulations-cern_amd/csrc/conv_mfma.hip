@@ -285,9 +285,14 @@ __device__ __forceinline__ void ring_loop_lean(int nk, char* smem, int slot_byte
 // [3][BN rows][64 B] (swizzled as the BK = 32 images), and the 8 waves are stacked along M (wave
 // tile BM/8 x BN): every A element is split by one wave only.
 //
-template <int MODE, int BM, int BN, bool SP, int BK = 64, typename T = bf16, int SPL = 0>
+// AFF (FWD only, es_conv2d_fwd_affine): the epilogue applies the per-output-channel affine and the
+// activation of ConvArgs.epi_* to acc + bias before the rounding to the output dtype (an eval-mode
+// BatchNorm -> LeakyReLU chain, neutron/generator.py:13-36, folded by es_bn_fold).  A template
+// parameter: the instantiations without it are the code they were before it existed.
+template <int MODE, int BM, int BN, bool SP, int BK = 64, typename T = bf16, int SPL = 0, bool AFF = false>
 __global__ void __launch_bounds__(RT) conv_ring_kernel(ConvArgs a) {
   static_assert(!SPL || (sizeof(T) == 4 && BK == 64), "split-fp32: fp32 operands, 128-byte slot rows");
+  static_assert(!AFF || MODE == MODE_FWD, "affine epilogue: FWD only");
   // (SPL 256 x 256: 2 x 4 waves of 128 x 64 and two 64 KiB slots; one step in flight covers a step
   // of 192 MFMAs per wave)
   constexpr bool SPB = SPL == 2;
@@ -798,6 +803,20 @@ __global__ void __launch_bounds__(RT) conv_ring_kernel(ConvArgs a) {
     const int ng = kc0 + j * 16 + col16;
     float bv = 0.f;
     if constexpr (MODE == MODE_FWD) bv = (a.bias && ng < a.Ng) ? a.bias[ng] : 0.f;
+    if constexpr (AFF) {
+      // scale * (acc + bias) + shift as one fma per value: shift' = scale * bias + shift
+      const float sc = ng < a.Ng ? a.epi_scale[ng] : 0.f;
+      const float sh = fmaf(bv, sc, ng < a.Ng ? a.epi_shift[ng] : 0.f);
+      const float neg = a.epi_act == ES_ACT_LRELU ? a.epi_slope : (a.epi_act == ES_ACT_RELU ? 0.f : 1.f);
+#pragma unroll
+      for (int i = 0; i < RM; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          float v = fmaf(acc[i][j][jj], sc, sh);
+          v = v > 0.f ? v : v * neg;
+          acc[i][j][jj] = a.out_bf16 ? (float)(bf16)v : v;
+        }
+    } else {
 #pragma unroll
     for (int i = 0; i < RM; ++i)
 #pragma unroll
@@ -805,6 +824,7 @@ __global__ void __launch_bounds__(RT) conv_ring_kernel(ConvArgs a) {
         const float v = acc[i][j][jj] + bv;
         acc[i][j][jj] = a.out_bf16 ? (float)(bf16)v : v;
       }
+    }
   }
   if (BK == 32 || a.vec_out) {   // (the host runs BK = 32 only with vec_out)
     // BatchNorm statistics of the stored values (conv -> BatchNorm fusion): per column, count /
@@ -1506,7 +1526,9 @@ __global__ void __launch_bounds__(RT) conv_persist_kernel(ConvArgs a, int ntiles
 //   * BatchNorm partials: per lane running sums / sums of squares of its 4 columns over all its
 //     tiles (fixed columns), merged across lanes and row waves once at the end: one [3][Ng]
 //     partial per (workgroup, class), chunks = 4 x 256.
-template <int NT>
+// AFF: the affine + activation epilogue of es_conv2d_fwd_affine (see conv_ring_kernel); the scale
+// table takes the first [BN] floats of the statistics area, which such a launch never uses.
+template <int NT, bool AFF = false>
 __global__ void __launch_bounds__(RT) conv_p256_kernel(ConvArgs a, int R) {
   constexpr int BM = 256, BN = 256, BK = 32, WGN = 4;
   constexpr int WM = 128, WN = 64, RM = WM / 16, RN = WN / 16, RMF = RM / 2;
@@ -1622,13 +1644,24 @@ __global__ void __launch_bounds__(RT) conv_p256_kernel(ConvArgs a, int R) {
   // the column tile's bias and the workgroup's statistics accumulators [2 row waves][3][BN] in LDS
   // (nothing of the epilogue stays in registers across the main loop), written through inline asm
   // like every epilogue LDS access (invisible to hipcc's DMA wait insertion)
+  if constexpr (AFF) {
+    // sbias holds shift' = scale * bias + shift, sst[0 .. BN) the scale (no statistics: stats_part NULL)
+    if (threadIdx.x < BN) {
+      const int gcol = n0 + threadIdx.x, ch = gcol - (gcol / a.Ng) * a.Ng;
+      const float sc = a.epi_scale[ch];
+      ds_write_f32_asm(sbias + threadIdx.x * 4, fmaf(a.bias ? a.bias[ch] : 0.f, sc, a.epi_shift[ch]));
+      ds_write_f32_asm(sst + threadIdx.x * 4, sc);
+    }
+  } else {
   if (threadIdx.x < BN) {
     const int gcol = n0 + threadIdx.x;
     ds_write_f32_asm(sbias + threadIdx.x * 4, a.bias ? a.bias[gcol - (gcol / a.Ng) * a.Ng] : 0.f);
   }
   for (int i = threadIdx.x; i < 2 * 3 * BN; i += RT) ds_write_f32_asm(sst + i * 4, 0.f);
+  }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  const bool want_stats = a.stats_part != nullptr;
+  const bool want_stats = !AFF && a.stats_part != nullptr;
+  const float eneg = a.epi_act == ES_ACT_LRELU ? a.epi_slope : (a.epi_act == ES_ACT_RELU ? 0.f : 1.f);
 
   struct Frag {
     bf16x8 a[RMF], b[RN];
@@ -1664,6 +1697,14 @@ __global__ void __launch_bounds__(RT) conv_p256_kernel(ConvArgs a, int R) {
     // use of it can be scheduled above the wait)
 #pragma unroll
     for (int j = 0; j < RN; ++j) asm volatile("" : "+v"(bcol[j]));
+    float scol[AFF ? RN : 1];
+    if constexpr (AFF) {
+#pragma unroll
+      for (int j = 0; j < RN; ++j) scol[j] = ds_read_f32_asm(sst + (wn0 + j * 16 + col16) * 4);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int j = 0; j < RN; ++j) asm volatile("" : "+v"(scol[j]));
+    }
     // store lanes: row lr8 (+ 8) of a pass, 16-byte chunk lch of the wave's 64 columns
     const int lr8 = le & 7, lch = le >> 3;
     float ts[8], ts2[8], npad = 0.f;
@@ -1677,7 +1718,14 @@ __global__ void __launch_bounds__(RT) conv_p256_kernel(ConvArgs a, int R) {
       for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
         for (int j = 0; j < RN; ++j) {
-          const bf16 vb = (bf16)(acc[i][j][jj] + bcol[j]);
+          float vf;
+          if constexpr (AFF) {
+            vf = fmaf(acc[i][j][jj], scol[j], bcol[j]);
+            vf = vf > 0.f ? vf : vf * eneg;
+          } else {
+            vf = acc[i][j][jj] + bcol[j];
+          }
+          const bf16 vb = (bf16)vf;
           ds_write_u16(stg_e + (rq + jj) * SPITCH + (j * 16 + col16) * 2, (uint32_t)__builtin_bit_cast(uint16_t, vb));
         }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -2742,11 +2790,25 @@ static void launch_wgrad_reduce(const float* ws, int splits, int K, int C, int R
 int64_t g_conv_launches = 0;
 extern "C" int64_t es_conv_launch_count() { return g_conv_launches; }
 
+// One ring launch; aff (FWD, bf16 or split-fp32 operands): the instantiation with the affine +
+// activation epilogue (es_conv2d_fwd_affine), which reports itself in g_aff_req.fused.
+template <int MODE, int BM, int BN, bool SP, int BK, typename T, int SPL>
+void launch_ring_grid(const ConvArgs& a, dim3 grid, hipStream_t st, bool aff) {
+  if constexpr (MODE == MODE_FWD && (sizeof(T) == 2 || SPL > 0)) {
+    if (aff) {
+      g_aff_req.fused = 1;
+      hipLaunchKernelGGL((conv_ring_kernel<MODE, BM, BN, SP, BK, T, SPL, true>), grid, dim3(RT), 0, st, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((conv_ring_kernel<MODE, BM, BN, SP, BK, T, SPL>), grid, dim3(RT), 0, st, a);
+}
+
 template <int MODE, int BM, int BN, bool SP, int BK = 64, typename T = bf16, int SPL = 0>
-void launch_ring(const ConvArgs& a, int row_tiles, hipStream_t st) {
+void launch_ring(const ConvArgs& a, int row_tiles, hipStream_t st, bool aff = false) {
   dim3 grid(row_tiles, (a.Ng + BN - 1) / BN, 1);
   ++g_conv_launches;
-  hipLaunchKernelGGL((conv_ring_kernel<MODE, BM, BN, SP, BK, T, SPL>), grid, dim3(RT), 0, st, a);
+  launch_ring_grid<MODE, BM, BN, SP, BK, T, SPL>(a, grid, st, aff);
 }
 
 // minimum K-steps per WGRAD K-split (each split flushes its whole fp32 tile with atomics; 8 / 32 / 64
@@ -2802,6 +2864,7 @@ bool g_p256 = true;
 }  // namespace
 
 thread_local StatsRequest g_stats_req;
+thread_local AffineRequest g_aff_req;
 thread_local BnRedRequest g_bnr_req;
 
 // Class geometry of the sub-pixel decomposition (see SubPixel): output row p belongs to class
@@ -2943,6 +3006,15 @@ int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
     a.b_src = (const char*)a.b_src + es_weight_planes_offset(nel);
   }
   constexpr int EB = sizeof(T);
+  // affine + activation epilogue requested (es_conv2d_fwd_affine): bf16 and split-fp32 FWD kernels
+  // carry it; the exact-fp32 ring does not (the caller then runs the norm pass)
+  const bool aff = mode == MODE_FWD && g_aff_req.scale != nullptr && (EB == 2 || SPL > 0);
+  if (aff) {
+    a.epi_scale = g_aff_req.scale;
+    a.epi_shift = g_aff_req.shift;
+    a.epi_act = g_aff_req.act;
+    a.epi_slope = g_aff_req.slope;
+  }
   // caller checked: channels % (128 / EB) == 0, K % (128 / EB) == 0 per step
   int PQ;
   if (mode == MODE_FWD) {
@@ -3066,6 +3138,13 @@ int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
         g_stats_req.chunks = 256 * 4;
       }
       ++g_conv_launches;
+      if (aff) {
+        g_aff_req.fused = 1;
+        if (NT == 1) hipLaunchKernelGGL((conv_p256_kernel<1, true>), dim3(256), dim3(RT), 0, st, a, row_tiles);
+        else if (NT == 2) hipLaunchKernelGGL((conv_p256_kernel<2, true>), dim3(256), dim3(RT), 0, st, a, row_tiles);
+        else hipLaunchKernelGGL((conv_p256_kernel<4, true>), dim3(256), dim3(RT), 0, st, a, row_tiles);
+        return 1;
+      }
       if (NT == 1) hipLaunchKernelGGL((conv_p256_kernel<1>), dim3(256), dim3(RT), 0, st, a, row_tiles);
       else if (NT == 2) hipLaunchKernelGGL((conv_p256_kernel<2>), dim3(256), dim3(RT), 0, st, a, row_tiles);
       else hipLaunchKernelGGL((conv_p256_kernel<4>), dim3(256), dim3(RT), 0, st, a, row_tiles);
@@ -3075,28 +3154,28 @@ int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
     if constexpr (SPL == 2) {   // 256 x 128 tiles (a wave's 128 columns within one class) or 256 x 64
       if (a.Ng % 128 == 0) {
         dim3 grid(row_tiles, 4 * a.Ng / 128, 1);
-        hipLaunchKernelGGL((conv_ring_kernel<MODE_FWD, 256, 128, true, 64, T, 2>), grid, dim3(RT), 0, st, a);
+        launch_ring_grid<MODE_FWD, 256, 128, true, 64, T, 2>(a, grid, st, aff);
       } else {
         dim3 grid(row_tiles, 4 * a.Ng / 64, 1);
-        hipLaunchKernelGGL((conv_ring_kernel<MODE_FWD, 256, 64, true, 64, T, 2>), grid, dim3(RT), 0, st, a);
+        launch_ring_grid<MODE_FWD, 256, 64, true, 64, T, 2>(a, grid, st, aff);
       }
     } else if constexpr (SPL) {   // 256 x 256 tiles of 32-channel steps
       dim3 grid(row_tiles, (4 * a.Ng + 255) / 256, 1);
-      hipLaunchKernelGGL((conv_ring_kernel<MODE_FWD, 256, 256, true, 64, T, 1>), grid, dim3(RT), 0, st, a);
+      launch_ring_grid<MODE_FWD, 256, 256, true, 64, T, 1>(a, grid, st, aff);
     } else {
       dim3 grid(row_tiles, (4 * a.Ng + 255) / 256, 1);
-      hipLaunchKernelGGL((conv_ring_kernel<MODE_FWD, 256, 256, true, 32, T>), grid, dim3(RT), 0, st, a);
+      launch_ring_grid<MODE_FWD, 256, 256, true, 32, T, 0>(a, grid, st, aff);
     }
     return 1;
   }
 #define ES_RING(MD, BMV, BNV)                                                                  \
-  (sp_weights ? launch_ring<MD, BMV, BNV, true, 64, T, SPL>(a, row_tiles, st)                         \
-              : launch_ring<MD, BMV, BNV, false, 64, T, SPL>(a, row_tiles, st))
+  (sp_weights ? launch_ring<MD, BMV, BNV, true, 64, T, SPL>(a, row_tiles, st, aff)                    \
+              : launch_ring<MD, BMV, BNV, false, 64, T, SPL>(a, row_tiles, st, aff))
   const bool wide = g_ring256 && big && !shortk && a.Ng >= 256 && a.ng >= 16 && a.vec_out &&
                     (sp_weights || mode == MODE_DGRAD);   // (plain FWD: register spills at 256 x 256)
   if constexpr (SPL == 1) if (wide) {   // split-fp32: 256 x 256 tiles of 32-channel steps
     if (mode == MODE_FWD) {   // (wide FWD is sub-pixel only)
-      launch_ring<MODE_FWD, 256, 256, true, 64, T, 1>(a, row_tiles, st);
+      launch_ring<MODE_FWD, 256, 256, true, 64, T, 1>(a, row_tiles, st, aff);
     } else {
       if (sp_weights) launch_ring<MODE_DGRAD, 256, 256, true, 64, T, 1>(a, row_tiles, st);
       else launch_ring<MODE_DGRAD, 256, 256, false, 64, T, 1>(a, row_tiles, st);
@@ -3104,15 +3183,20 @@ int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
     return 1;
   }
   if constexpr (SPL == 2) if (wide) {   // pre-split B: 256 x 128 tiles (256 x 256 does not fit the LDS)
-    if (mode == MODE_FWD) launch_ring<MODE_FWD, 256, 128, true, 64, T, 2>(a, row_tiles, st);
+    if (mode == MODE_FWD) launch_ring<MODE_FWD, 256, 128, true, 64, T, 2>(a, row_tiles, st, aff);
     else if (sp_weights) launch_ring<MODE_DGRAD, 256, 128, true, 64, T, 2>(a, row_tiles, st);
     else launch_ring<MODE_DGRAD, 256, 128, false, 64, T, 2>(a, row_tiles, st);
     return 1;
   }
   if constexpr (!SPL) if (wide) {
     if (mode == MODE_FWD) {
-      if (sp_weights) launch_ring<MODE_FWD, 256, 256, true, 32, T>(a, row_tiles, st);
-      else launch_ring<MODE_FWD, 256, 256, false, 32, T>(a, row_tiles, st);
+      if (sp_weights) launch_ring<MODE_FWD, 256, 256, true, 32, T>(a, row_tiles, st, aff);
+      else {   // (not reached: wide FWD is sub-pixel only; launched directly so that no affine variant of
+               // this tile, which spills registers, is instantiated)
+        dim3 grid(row_tiles, (a.Ng + 255) / 256, 1);
+        ++g_conv_launches;
+        hipLaunchKernelGGL((conv_ring_kernel<MODE_FWD, 256, 256, false, 32, T>), grid, dim3(RT), 0, st, a);
+      }
     } else {
       if (sp_weights) launch_ring<MODE_DGRAD, 256, 256, true, 32, T>(a, row_tiles, st);
       else launch_ring<MODE_DGRAD, 256, 256, false, 32, T>(a, row_tiles, st);
@@ -3381,6 +3465,8 @@ extern "C" int es_conv_set_wgrad_ws(int on) {
   g_wgrad_ws = on ? 1 : 0;
   return old;
 }
+
+int es_f32_split_level() { return g_f32_split; }
 
 extern "C" int es_conv_set_f32_split(int on) {
   const int old = g_f32_split;

@@ -1126,6 +1126,7 @@ extern "C" int64_t es_struct_size(int which) {
     case 6: return sizeof(es_dfront2_params_t);
     case 7: return sizeof(es_dmlp_params_t);
     case 8: return sizeof(es_pack_job_t);
+    case 9: return sizeof(es_affine_t);
     default: return -1;
   }
 }

@@ -77,6 +77,10 @@ class PackJob(C.Structure):
                 ("mode", C.c_int), ("dt", C.c_int), ("planes", C.c_int), ("out", C.c_void_p)]
 
 
+class Affine(C.Structure):
+    _fields_ = [("scale", C.c_void_p), ("shift", C.c_void_p), ("act", C.c_int), ("slope", C.c_float)]
+
+
 P = C.c_void_p
 I64 = C.c_int64
 _SIGS = {
@@ -93,6 +97,7 @@ _SIGS = {
     "es_subpixel_taps": (C.c_int, [C.c_int, C.c_int]),
     "es_conv2d_fwd": (C.c_int, [P, C.c_int, P, P, P, P, P, C.c_int, P, P]),
     "es_conv2d_fwd_stats": (C.c_int, [P, C.c_int, P, P, P, P, P, C.c_int, P, P, I64, P, P]),
+    "es_conv2d_fwd_affine": (C.c_int, [P, C.c_int, P, P, P, P, P, P, C.c_int, P, P, P]),
     "es_conv2d_dgrad": (C.c_int, [P, C.c_int, P, P, P, P, C.c_int, P, C.c_float, P]),
     "es_conv2d_dgrad_bnred": (C.c_int, [P, C.c_int, P, P, P, P, C.c_int, P, P, P, P, P, I64, P, P]),
     "es_conv2d_wgrad": (C.c_int, [P, C.c_int, P, P, P, P, P, P]),
@@ -190,6 +195,9 @@ _SIGS = {
     "es_expert_plan": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "es_div_by": (C.c_int, [P, C.c_int, P, P]),
     "es_struct_size": (I64, [C.c_int]),
+    "es_bn_fold": (C.c_int, [P, P, P, P, C.c_int, C.c_float, P, P, P]),
+    "es_bn_fold_batch": (C.c_int, [C.c_int, P, P, P, P, P, P, P, P, P]),
+    "es_sim_finish": (C.c_int, [P, P, P, P, P, C.c_int, P, P, P]),
     "es_dropout_mask": (C.c_int, [P, I64, P, P]),
 }
 
@@ -202,7 +210,7 @@ def lib_path() -> str:
     return _LIB_PATH
 
 
-_ABI_STRUCTS = (View, Dropout, ConvDesc, Norm, Chain, GenLoss, DFront2Params, DMlpParams, PackJob)
+_ABI_STRUCTS = (View, Dropout, ConvDesc, Norm, Chain, GenLoss, DFront2Params, DMlpParams, PackJob, Affine)
 
 
 def lib():

@@ -462,6 +462,41 @@ class ConvOp:
                          hip.ptr(bias), out.ptr, out.dt, hip.strides4(out.strides), hip.stream_ptr())
         return out
 
+    def fwd_affine(self, x: Act, affine: "EvalAffine", out_dtype=None, fused=True) -> Act:
+        """Eval path: act(scale * (conv(x) + bias) + shift), the conv followed by an eval-mode
+        BatchNorm -> activation chain folded into ``affine`` (fold_batchnorms).  fused: ask the conv
+        kernel for the epilogue (es_conv2d_fwd_affine); when it reports that it did not apply it, or
+        with fused=False, the plain conv output goes through one es_norm_act_fwd pass of the same
+        affine instead."""
+        assert self._plain is None, "fwd_affine: resized convs are not on an affine (BatchNorm) path"
+        xv = self._pixel_view(x)
+        if xv is not None:
+            o = self.fwd_affine(xv, affine, out_dtype, fused)
+            return Act(o.t, (x.dims[0], self.K, 1, 1), (self.K, 1, 1, 1))
+        cdt = x.t.dtype
+        if fused:
+            d = self.desc(x)
+            if self.subpixel(d, cdt):
+                d.subpixel = 1
+                wk = self.packed(cdt, 2)
+            else:
+                wk = self.packed(cdt, 0)
+            out = Act.nhwc(d.N, d.K, d.P, d.Q, out_dtype or cdt, x.t.device)
+            out.px = x.px
+            epi = affine.struct()
+            flag = C.c_int(0)
+            with _probed(self.label and self.label + ".fwd"):
+                hip.call("es_conv2d_fwd_affine", C.byref(d), x.dt, x.ptr, hip.strides4(x.strides), hip.ptr(wk),
+                         hip.ptr(self.bias), C.byref(epi), out.ptr, out.dt, hip.strides4(out.strides),
+                         C.byref(flag), hip.stream_ptr())
+            if flag.value:
+                return out
+            h = out
+        else:
+            h = self.fwd(x)
+            h.px = x.px
+        return affine.apply(h, out_dtype or cdt)
+
     def _pixel_view(self, x: Act):
         """A wide linear ([B, C] -> [B, K], K >= 1024) as a 1x1 conv over 16-pixel images of the same
         memory, NHWC (B/16, C, 16, 1): the ring FWD kernels (conv_mfma.hip) tile rows as (image group,
@@ -822,6 +857,65 @@ class NormOp:
         if dsum is not None and x.dims[1] > 1024:
             channel_sum(dx, dsum, 1.0)
         return dx
+
+
+# ------------------------------------------------------------------- eval-mode BatchNorm, folded
+class EvalAffine:
+    """An eval-mode BatchNorm -> activation chain as a per-channel affine (es_affine_t): scale / shift
+    are views of a FoldedNorms buffer that fold() refreshes from the running statistics."""
+
+    def __init__(self, scale, shift, zeros, ones, act=hip.ACT_LRELU, slope=0.1):
+        self.scale, self.shift, self.zeros, self.ones, self.act, self.slope = scale, shift, zeros, ones, act, slope
+
+    def struct(self) -> hip.Affine:
+        a = hip.Affine()
+        a.scale, a.shift, a.act, a.slope = self.scale.data_ptr(), self.shift.data_ptr(), self.act, self.slope
+        return a
+
+    def apply(self, h: Act, out_dtype=None) -> Act:
+        """The unfused form: one es_norm_act_fwd pass of the same affine over a conv output h (a
+        BatchNorm with mean 0, invstd 1, gamma = scale, beta = shift)."""
+        nm = hip.Norm()
+        nm.kind, nm.groups = hip.NORM_BN, 1
+        nm.mean, nm.invstd = self.zeros.data_ptr(), self.ones.data_ptr()
+        nm.gamma, nm.beta = self.scale.data_ptr(), self.shift.data_ptr()
+        chain = hip.chain_struct(self.act, self.slope)
+        y = Act(torch.empty(h.t.numel(), dtype=out_dtype or h.t.dtype, device=h.t.device), h.dims, h.strides, h.sample)
+        hip.call("es_norm_act_fwd", C.byref(h.view), h.dt, C.byref(nm), C.byref(chain), None, 0, None, h.ptr,
+                 C.byref(y.view), y.dt, y.ptr, hip.stream_ptr())
+        return y
+
+
+class FoldedNorms:
+    """The BatchNorms of one module folded for its eval path: one persistent device buffer holding
+    every norm's scale and shift (the same storage at every call, so a captured graph re-reads it),
+    refreshed from the current gamma / beta / running statistics by ONE es_bn_fold_batch launch."""
+
+    def __init__(self, norms, act=hip.ACT_LRELU, slope=0.1):
+        assert 0 < len(norms) <= 8 and all(n.kind == hip.NORM_BN for n in norms)
+        self.norms = list(norms)
+        dev = norms[0].rv.device
+        cs = [int(n.rv.numel()) for n in norms]
+        total, cmax = sum(cs), max(cs)
+        self.buf = torch.zeros(2 * total + 2 * cmax, dtype=torch.float32, device=dev)
+        zeros = self.buf[2 * total:2 * total + cmax]
+        ones = self.buf[2 * total + cmax:]
+        ones.fill_(1.0)
+        self.affines, o = [], 0
+        for c in cs:
+            self.affines.append(EvalAffine(self.buf[o:o + c], self.buf[total + o:total + o + c], zeros, ones, act, slope))
+            o += c
+        n = len(norms)
+        arr = lambda vals: (C.c_void_p * n)(*vals)
+        self._args = (n, arr([m.gamma.data_ptr() if m.gamma is not None else None for m in norms]),
+                      arr([m.beta.data_ptr() if m.beta is not None else None for m in norms]),
+                      arr([m.rm.data_ptr() for m in norms]), arr([m.rv.data_ptr() for m in norms]),
+                      (C.c_int * n)(*cs), (C.c_float * n)(*[float(m.eps) for m in norms]),
+                      arr([a.scale.data_ptr() for a in self.affines]), arr([a.shift.data_ptr() for a in self.affines]))
+
+    def fold(self):
+        hip.call("es_bn_fold_batch", *self._args, hip.stream_ptr())
+        return self.affines
 
 
 def act_fwd(x: Act, chain: hip.Chain, out: Act = None, out_dtype=None) -> Act:

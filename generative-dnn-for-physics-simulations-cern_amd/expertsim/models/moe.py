@@ -630,9 +630,163 @@ class MoEWrapper(nn.Module):
                "ws_std": ws_std, **{f"ws_std_{i}": ws_std_exp[i] for i in range(self.n_experts)}, "epoch": epoch}
         return log
 
+    # ---------------------------------------------------------------------------- simulation
+    # Philox stream ids of the simulation draws (DeviceRNG's step streams start at 1 << 24)
+    SIM_NOISE_STREAM = 0x51D00001
+    SIM_GUMBEL_STREAM = 0x51D00002
+
+    @torch.no_grad()
+    def simulate(self, cond, *, seed=0, sample_offset=0, noise=None, batch_size=None, domain="photons",
+                 routing="sample", sums=False, fused=True, graph=True):
+        """Fast simulation: conditions in, calorimeter images out (the reference's routed prediction,
+        train/utils.py:208-266 get_predictions_from_experts_results, on the device).
+
+        cond [N, cond_dim] -> {"images" [N,H,W] fp32 in the order of cond (photons: expm1 of the
+        generator's log1p-domain output; log: that output), "expert" [N] int32, "noise" [N, noise_dim],
+        and with sums=True "sums" [N,5] fp64, the five channel sums of the photon images}, all on the
+        device.  Per chunk of batch_size conditions (default eval_batch_size; the last may be short):
+        router forward -> routing ("sample": the stochastic Gumbel at tau = 1 of evaluate / moe.py:650;
+        "argmax": argmax of the logits) -> es_router_dispatch, and per expert, serially on the
+        current stream, es_gather_rows_at of [noise | cond] with the expert's device count ->
+        generator.infer(rows=count) -> es_sim_finish into the batch-ordered outputs.  No host round
+        trip: an expert without rows costs launches but no work.
+
+        Determinism: sample i's noise is es_randn_dev(seed) at element offset (sample_offset + i) *
+        noise_dim, and its Gumbel draw es_rand_exponential_dev(seed) at (sample_offset + i) * E, so both
+        depend on (seed, sample_offset + i) only, not on the chunking or the routing of other samples;
+        noise= injects the rows instead.  A rank of a data-parallel job passes its own sample_offset.
+        graph=True: the chunk program (router to finish) is captured once per (chunk size, domain, sums,
+        fused, routing) on one stream and replayed; the chunk's cond / noise / Gumbel draws are written
+        into its static input buffers before each replay.
+        Changes no training state: parameters, running statistics, batch counters, step counters and
+        optimizers are only read."""
+        if domain not in ("photons", "log"):
+            raise ValueError(f"simulate: domain must be photons or log, got {domain!r}")
+        if routing not in ("sample", "argmax"):
+            raise ValueError(f"simulate: routing must be sample or argmax, got {routing!r}")
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise hip.HipError("MoEWrapper.simulate runs on the HIP device only (no CPU fallback)")
+        cond = torch.as_tensor(cond).to(device=dev, dtype=torch.float32).contiguous()
+        N, nd, E = cond.shape[0], self.noise_dim, self.n_experts
+        H, W = self.generators[0].image_shape
+        if noise is not None:
+            noise = torch.as_tensor(noise).to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(noise.shape) != (N, nd):
+                raise ValueError(f"simulate: noise must be [{N}, {nd}], got {tuple(noise.shape)}")
+        out = {"images": torch.empty(N, H, W, dtype=torch.float32, device=dev),
+               "expert": torch.zeros(N, dtype=torch.int32, device=dev),
+               "noise": torch.empty(N, nd, dtype=torch.float32, device=dev)}
+        if sums:
+            out["sums"] = torch.empty(N, 5, dtype=torch.float64, device=dev)
+        set_deterministic(self.precision == "fp32" and self.deterministic)
+        set_f32_split(self.fp32_mfma == "split")
+        for start, n, roff, eoff in simulate_plan(N, batch_size or self.eval_batch_size, sample_offset, nd, E):
+            key = (n, domain, bool(sums), bool(fused), routing)
+            st = self._sim_state(key, dev, H, W)
+            st["cond"].copy_(cond[start:start + n])
+            if noise is not None:
+                st["noise"].copy_(noise[start:start + n])
+            else:
+                hip.call("es_randn_dev", hip.ptr(st["noise"]), n * nd, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                         self.SIM_NOISE_STREAM, None, 0, roff, hip.stream_ptr())
+            if E > 1 and routing == "sample":
+                hip.call("es_rand_exponential_dev", hip.ptr(st["expo"]), n * E, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                         self.SIM_GUMBEL_STREAM, None, 0, eoff, hip.stream_ptr())
+            if not graph or torch.cuda.is_current_stream_capturing():
+                self._sim_chunk(st, key)
+            else:
+                if st["graph"] is None:
+                    # one eager run first (weight packings, folded-norm buffers and the router's ops then
+                    # exist outside the graph), then the capture on a side stream, as torch prescribes
+                    self._sim_chunk(st, key)
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self._sim_chunk(st, key)
+                    st["graph"] = g
+                    self.sim_captures += 1
+                else:
+                    self.sim_replays += 1
+                st["graph"].replay()
+            out["images"][start:start + n].copy_(st["images"])
+            out["noise"][start:start + n].copy_(st["noise"])
+            if E > 1:
+                out["expert"][start:start + n].copy_(st["expert"])
+            if sums:
+                out["sums"][start:start + n].copy_(st["sums"])
+        return out
+
+    sim_captures = 0
+    sim_replays = 0
+
+    def _sim_state(self, key, dev, H, W):
+        """The static buffers (and the graph) of one chunk program."""
+        cache = self.__dict__.setdefault("_sim", {})
+        st = cache.get(key)
+        if st is None or st["cond"].device != dev:
+            n, E, nd = key[0], self.n_experts, self.noise_dim
+            cd = int(self.generators[0].cond_dim)
+            buf = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            st = cache[key] = {
+                "cond": buf((n, cd), torch.float32), "noise": buf((n, nd), torch.float32),
+                # argmax routing: Exp(1) draws of 1 make the Gumbel term log(1) = 0
+                "expo": torch.ones(n, max(E, 1), dtype=torch.float32, device=dev),
+                "x0": buf((n, nd + cd), torch.float32), "images": buf((n, H, W), torch.float32),
+                "sums": buf((n, 5), torch.float64), "expert": torch.zeros(n, dtype=torch.int32, device=dev),
+                "perm": buf((n,), torch.int32), "offs": buf((E + 1,), torch.int32),
+                "counts": torch.zeros(E, dtype=torch.int32, device=dev), "graph": None}
+        return st
+
+    def _sim_chunk(self, st, key):
+        """One chunk: router, dispatch, per-expert gather / infer / finish (all on the current stream)."""
+        n, domain, sums, fused, _ = key
+        E, nd = self.n_experts, self.noise_dim
+        photons = 1 if domain == "photons" else 0
+        x0 = st["x0"]
+        copy_act(Act.of(st["noise"]), Act.of(x0[:, :nd]))
+        copy_act(Act.of(st["cond"]), Act.of(x0[:, nd:]))
+        sums_ptr = hip.ptr(st["sums"]) if sums else None
+        if E == 1:
+            h6 = self.generators[0].infer(x0, rows=None, fused=fused)
+            hip.call("es_sim_finish", C.byref(h6.view), h6.ptr, None, None, None, photons, hip.ptr(st["images"]),
+                     sums_ptr, hip.stream_ptr())
+            return
+        _, _, idx, counts, _ = self.router.fwd(st["cond"], st["expo"], 1.0)
+        st["expert"].copy_(idx)
+        st["counts"].copy_(counts)
+        perm, offs, cnt = st["perm"], st["offs"], st["counts"]
+        hip.call("es_router_dispatch", hip.ptr(idx), n, E, hip.ptr(perm), hip.ptr(offs), hip.stream_ptr())
+        for e in range(E):
+            live = cnt[e:e + 1]
+            rows = _gather_rows(x0, (perm, offs[e:e + 1]), n, x0.shape[1], live)
+            h6 = self.generators[e].infer(rows, rows=live, fused=fused)
+            v = hip.make_view(h6.dims, h6.strides, False)
+            hip.call("es_sim_finish", C.byref(v), h6.ptr, hip.ptr(live), hip.ptr(perm), hip.ptr(offs[e:e + 1]),
+                     photons, hip.ptr(st["images"]), sums_ptr, hip.stream_ptr())
+
     def get_expert_assignment_counts(self, expert_assignments: torch.Tensor) -> torch.Tensor:
         counts = torch.bincount(expert_assignments.long(), minlength=self.n_experts).float()
         return counts / expert_assignments.size(0)
+
+
+def simulate_plan(num, batch_size, sample_offset=0, noise_dim=10, n_experts=1):
+    """The chunks of MoEWrapper.simulate (a pure host function): [(start, size, randn element offset,
+    exponential element offset)] for `num` conditions in chunks of `batch_size` (the last may be short).
+    Sample i draws its noise at element (sample_offset + i) * noise_dim and its Gumbel terms at
+    (sample_offset + i) * n_experts, whatever the chunking; es_randn_dev draws pairs, so every
+    chunk's first noise element must be even."""
+    num, batch_size, sample_offset = int(num), int(batch_size), int(sample_offset)
+    if num < 0 or batch_size <= 0 or sample_offset < 0:
+        raise ValueError(f"simulate_plan: bad sizes num={num} batch_size={batch_size} sample_offset={sample_offset}")
+    plan = []
+    for start in range(0, num, batch_size):
+        roff = (sample_offset + start) * int(noise_dim)
+        if roff % 2:
+            raise ValueError(f"simulate: chunk at sample {sample_offset + start} starts at the odd noise element "
+                             f"{roff} (es_randn_dev draws pairs): use an even batch_size / sample_offset or noise_dim")
+        plan.append((start, min(batch_size, num - start), roff, (sample_offset + start) * int(n_experts)))
+    return plan
 
 
 def _gather_rows(t: torch.Tensor, ridx, rows: int, cols: int, live=None) -> torch.Tensor:

@@ -18,13 +18,14 @@ Dropout masks come from Philox streams (expertsim/utils/philox.py), layer index 
 from __future__ import annotations
 
 
+import contextlib
 import ctypes as C
 
 import torch
 from torch import nn
 
 from ... import hip
-from ...layers import Act, ConvOp, NormOp, Upsample, act_bwd, act_fwd, copy_act
+from ...layers import Act, ConvOp, FoldedNorms, NormOp, Upsample, act_bwd, act_fwd, copy_act
 from ...utils import philox
 from ..base import ExpertModule, build_tree, get_module
 
@@ -153,6 +154,39 @@ class GeneratorNeutron(ExpertModule):
         ctx = dict(x0=x0, h1=h1, y1=y1, s1=s1, h2=h2, y2=y2, s2=s2, y2n=y2n, h3=h3, y3=y3, s3=s3,
                    h4=h4, y4=y4, s4=s4, h5=h5, y5=y5, s5=s5, h6=h6, ch=ch, keep=keep)
         return img, ctx
+
+    # --------------------------------------------------------------------------- inference
+    def infer(self, x0_rows: torch.Tensor, rows: torch.Tensor = None, fused=True) -> Act:
+        """Simulation forward: x0_rows = [noise | cond] rows [B, noise_dim + cond_dim] fp32 (device) ->
+        h6, the pre-ReLU output of the last conv, Act [B,1,H,W] fp32 (es_sim_finish applies the ReLU).
+
+        The program of fwd(train=False) -- the reference's model.eval() forward, generator.py:42-49 --
+        without a ctx, keep-bit buffers or dropout structs: every eval-mode BatchNorm is a per-channel
+        affine folded from the CURRENT running statistics by one es_bn_fold_batch launch per call
+        (so a replayed graph sees them too) and, with fused=True, applied with the LeakyReLU in the
+        epilogue of the conv that feeds it (es_conv2d_fwd_affine; a kernel without that epilogue
+        falls back to one norm pass).  fused=False: every conv followed by its norm pass.
+        rows (device int32 [1]): the live count of the B-capacity batch (dynamic rows)."""
+        o = self.ops()
+        fold = o.get("_fold")
+        if fold is None:
+            fold = o["_fold"] = FoldedNorms([o[k] for k in ("bn1", "bn2", "bn3", "bn4", "bn5")], hip.ACT_LRELU, SLOPE)
+        k, F2 = self.base, self.fc2_features
+        cdt = self.compute_dtype
+        dev = x0_rows.device
+        B = x0_rows.shape[0]
+        a1, a2, a3, a4, a5 = fold.fold()
+        scope = hip.live_rows(B, rows, rows) if rows is not None else contextlib.nullcontext()
+        with scope:
+            y = copy_act(Act.of(x0_rows), Act.rows(B, self.noise_dim + self.cond_dim, cdt, dev))
+            y = o["fc1"].fwd_affine(y, a1, fused=fused)
+            y = o["fc2"].fwd_affine(y, a2, fused=fused)
+            # [B, 21632] rows are NCHW [B,128,k,k]; re-layout to NHWC for the vector gather
+            y = copy_act(Act(y.t, (B, 128, k, k), (F2, k * k, k, 1)), Act.nhwc(B, 128, k, k, cdt, dev))
+            y = o["c0"].fwd_affine(y, a3, fused=fused)
+            y = o["c5"].fwd_affine(y, a4, fused=fused)
+            y = o["c9"].fwd_affine(y, a5, fused=fused)
+            return o["c13"].fwd(y, out_dtype=torch.float32)
 
     # --------------------------------------------------------------------------- backward
     def bwd(self, ctx, dimg: Act, ready=None):

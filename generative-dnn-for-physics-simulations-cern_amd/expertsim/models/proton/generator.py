@@ -85,6 +85,29 @@ class Generator(ExpertModule):
         img = act_fwd(c["h6"], hip.chain_struct(hip.ACT_RELU))
         return img, c
 
+    def infer(self, x0_rows: torch.Tensor, rows: torch.Tensor = None, fused=True) -> Act:
+        """Simulation forward (the interface of GeneratorNeutron.infer): [noise | cond] rows [B, 19] fp32
+        -> the pre-ReLU output of the last conv, Act [B,1,56,30] fp32.  The program of fwd() -- the
+        reference's model.eval() forward, proton/generator.py:44-52 -- without a ctx.  LayerNorm and
+        GroupNorm take per-sample statistics, so nothing folds into the convs: ``fused`` is accepted
+        and has no effect.  rows (device int32 [1]): the live count of the B-capacity batch."""
+        import contextlib
+        o = self.ops()
+        cdt = self.compute_dtype
+        dev = x0_rows.device
+        B = x0_rows.shape[0]
+        lr = hip.chain_struct(hip.ACT_LRELU, SLOPE)
+        scope = hip.live_rows(B, rows, rows) if rows is not None else contextlib.nullcontext()
+        with scope:
+            y = copy_act(Act.of(x0_rows), Act.rows(B, self.noise_dim + self.cond_dim, cdt, dev))
+            y, _ = o["ln1"].fwd(o["fc1"].fwd(y), lr)
+            y, _ = o["ln2"].fwd(o["fc2"].fwd(y), lr)
+            y = copy_act(Act(y.t, (B, 512, 18, 10), (FEAT, 180, 10, 1)), Act.nhwc(B, 512, 18, 10, cdt, dev))
+            y, _ = o["gn1"].fwd(o["c1"].fwd(y), lr)
+            y, _ = o["gn2"].fwd(o["c5"].fwd(y), lr)
+            y, _ = o["gn3"].fwd(o["c8"].fwd(y), lr)
+            return o["c11"].fwd(y, out_dtype=torch.float32)
+
     def bwd(self, c, dimg: Act, ready=None):
         """ready(name): gradients from parameter ``name`` to the end of the flat buffer are final."""
         ready = ready or (lambda name: None)

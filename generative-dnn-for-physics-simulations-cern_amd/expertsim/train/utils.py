@@ -6,6 +6,7 @@ Same names, arguments and return conventions as the reference:
   get_max_value_image_coordinates(img)              train/utils.py:81-82
   calculate_joint_ws_across_experts(...)            train/utils.py:117-176
   get_predictions_from_generator_results(...)       train/utils.py:179-205
+  get_predictions_from_experts_results(...)         train/utils.py:208-266   (routed, device-side dispatch)
 
 MI355X design: the generated images never leave the device.  Each generator batch is produced in
 HBM (eval mode: BatchNorm running statistics, no dropout), and the fused HIP kernel
@@ -142,6 +143,58 @@ def get_predictions_from_generator_results(batch_size, num_samples, noise_dim, d
         res[start:end] = np.expm1(r).reshape(-1, *shape_images)
         raw[start:end] = r.reshape(-1, *shape_images)
     return res, raw
+
+
+@torch.no_grad()
+def get_predictions_from_experts_results(num_samples, noise_dim, device, y_test, router_network, experts,
+                                         shape_images=(56, 30), input_noise=None, input_expo=None,
+                                         batch_size=1024):
+    """Reference API (train/utils.py:208-266): the routed photon-domain prediction, host float64
+    [num_samples, *shape_images] -- each condition goes to the expert the router picks (argmax of its
+    Gumbel-softmax gates, as the reference's ``router_network(y)``), that expert's generator runs in
+    eval mode on fresh noise, and expm1 of its image lands at the condition's position.
+
+    Built on the pieces of MoEWrapper.simulate: es_router_dispatch (no ``np.where`` round trip), per
+    expert es_gather_rows_at of [noise | cond] with the expert's device count, generator.infer on
+    dynamic rows and es_sim_finish (relu, expm1, scatter).  Generalised from the reference's five
+    hard-coded experts to ``len(experts)``.  The reference's fifth expert reuses expert 2's indices
+    (``indx_4 = np.where(predicted_expert == 2)``, utils.py:222,228), so its expert 4 overwrites expert
+    2's predictions and conditions routed to expert 4 stay zero; that is not copied: expert e gets
+    the conditions routed to e.
+    input_noise [N, noise_dim] / input_expo [N, E] (Exp(1) draws of the Gumbel term; ones give the
+    argmax of the logits) inject the random draws (tests); default: device Philox draws."""
+    from ..models.moe import _gather_rows
+    from ..rng import default_rng
+    y = _cond_on(y_test, device)[:num_samples].contiguous()
+    E = len(experts)
+    H, W = shape_images
+    out = torch.empty(num_samples, H, W, dtype=torch.float32, device=y.device)
+    for start in range(0, num_samples, batch_size):
+        end = min(start + batch_size, num_samples)
+        n = end - start
+        yc = y[start:end].contiguous()
+        if input_noise is not None:
+            noise = _cond_on(input_noise[start:end], y.device)
+        else:
+            noise = torch.randn(n, noise_dim, device=y.device)
+        x0 = torch.cat([noise, yc], dim=1).contiguous()
+        if input_expo is not None:
+            expo = _cond_on(input_expo[start:end], y.device).contiguous()
+        else:
+            expo = default_rng().exponential(torch.empty(n, E, dtype=torch.float32, device=y.device))
+        _, _, idx, counts, _ = router_network.fwd(yc, expo, 1.0)
+        perm = torch.empty(n, dtype=torch.int32, device=y.device)
+        offs = torch.empty(E + 1, dtype=torch.int32, device=y.device)
+        hip.call("es_router_dispatch", hip.ptr(idx), n, E, hip.ptr(perm), hip.ptr(offs), hip.stream_ptr())
+        dst = out[start:end]
+        for e, gen in enumerate(experts):
+            live = counts[e:e + 1]
+            rows = _gather_rows(x0, (perm, offs[e:e + 1]), n, x0.shape[1], live)
+            h6 = gen.infer(rows, rows=live)
+            v = hip.make_view(h6.dims, h6.strides, False)
+            hip.call("es_sim_finish", C.byref(v), h6.ptr, hip.ptr(live), hip.ptr(perm), hip.ptr(offs[e:e + 1]), 1,
+                     hip.ptr(dst), None, hip.stream_ptr())
+    return out.double().cpu().numpy().reshape(num_samples, *shape_images)
 
 
 def calculate_joint_ws_across_experts(n_calc, x_tests: List, y_tests: List, generators: List, ch_org,

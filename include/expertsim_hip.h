@@ -144,6 +144,27 @@ int es_conv2d_fwd(const es_conv_desc_t* d, es_dtype_t dt, const void* x, const i
 int es_conv2d_fwd_stats(const es_conv_desc_t* d, es_dtype_t dt, const void* x, const int64_t xs[4],
                         const void* wk, const float* bias, void* y, es_dtype_t ydt, const int64_t ys[4],
                         float* part, int64_t part_floats, int* chunks, es_stream_t stream);
+/* Per-output-channel affine + activation applied to a conv's fp32 accumulator (indexed by output
+ * channel k): an eval-mode BatchNorm (a per-channel affine of the running statistics, es_bn_fold)
+ * and the LeakyReLU behind it, i.e. the reference's Conv / Linear -> BatchNorm -> Dropout (identity
+ * in eval) -> LeakyReLU chains (neutron/generator.py:13-36) in model.eval(). */
+typedef struct {
+  const float* scale; /* [K] */
+  const float* shift; /* [K] */
+  int act;            /* ES_ACT_* */
+  float slope;        /* LeakyReLU negative slope */
+} es_affine_t;
+/* es_conv2d_fwd with the epilogue y = act(scale[k] * (acc + bias[k]) + shift[k]) applied before the
+ * rounding to ydt (evaluated as one fma with shift' = scale * bias + shift).  Replaces
+ * aten::convolution / addmm + the eval-mode aten::native_batch_norm + leaky_relu of
+ * neutron/generator.py:13-36 on the simulation path (train/utils.py:179-266).
+ * *fused = 1: the kernel that ran applied the epilogue (the ring FWD kernels of conv_mfma.hip, bf16
+ * and split-fp32 operands).  *fused = 0: y holds the plain conv + bias output, bit-identical to
+ * es_conv2d_fwd, and the caller runs es_norm_act_fwd with the running statistics.
+ * d->rows / rows_px as es_conv2d_fwd: images past the live count are neither read nor written. */
+int es_conv2d_fwd_affine(const es_conv_desc_t* d, es_dtype_t dt, const void* x, const int64_t xs[4],
+                         const void* wk, const float* bias, const es_affine_t* epi, void* y, es_dtype_t ydt,
+                         const int64_t ys[4], int* fused, es_stream_t stream);
 /* dxu[n,c,hu,wu] = sum_{k,r,s} dy[n,k,p,q] * W[k,c,r,s] over (hu+pad-r) = p*stride, ...
  * (gradient w.r.t. the UPSAMPLED input; es_upsample_bwd folds it to the source grid).  With
  * integer factors d->up_h/up_w the fold happens inside the GEMM (K grows by up_h*up_w) and the
@@ -637,8 +658,8 @@ int es_expert_plan(const int32_t* counts, const int32_t* counts_all, int world, 
                    int min_local, int32_t* rows, int32_t* active, int32_t* n0, float* w, float* gcnt,
                    float* lcnt, es_stream_t stream);
 /* sizeof of the ABI structs (0 es_view_t, 1 es_dropout_t, 2 es_conv_desc_t, 3 es_norm_t, 4 es_chain_t,
- * 5 es_gen_loss_t, 6 es_dfront2_params_t, 7 es_dmlp_params_t; -1 unknown): the bindings check their
- * mirrors against it on load. */
+ * 5 es_gen_loss_t, 6 es_dfront2_params_t, 7 es_dmlp_params_t, 8 es_pack_job_t, 9 es_affine_t;
+ * -1 unknown): the bindings check their mirrors against it on load. */
 int64_t es_struct_size(int which);
 /* x[i] /= max(d[0], 1) for i < n (a sum over an expert's global batch -> its mean, d = the device count) */
 int es_div_by(float* x, int n, const float* d, es_stream_t stream);
@@ -657,6 +678,33 @@ int es_dropout_mask(uint8_t* out, int64_t n, const es_dropout_t* d, es_stream_t 
  * computes it; log_domain != 0 applies expm1 first (moe.py:646, train/utils.py:198). */
 int es_channel_sums(const es_view_t* x, es_dtype_t dt, const void* xp, int log_domain, double* out,
                     es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
+ * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
+ * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
+ * ---------------------------------------------------------------------------------------- */
+/* Eval-mode BatchNorm as a per-channel affine: scale[c] = gamma[c] * rsqrt(running_var[c] + eps),
+ * shift[c] = beta[c] - running_mean[c] * scale[c] (gamma / beta NULL: 1 / 0).  Replaces the
+ * aten::rsqrt / mul / sub of an eval-mode native_batch_norm (neutron/generator.py:13,19,26,31,35). */
+int es_bn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+               int C, float eps, float* scale, float* shift, es_stream_t stream);
+/* es_bn_fold for n <= ES_BN_FOLD_MAX BatchNorms (all those of one generator) in ONE launch; the arrays
+ * are host arrays of device pointers / sizes, as es_sn_power_iter_batch takes them.  Same values as
+ * n single calls, bit for bit. */
+#define ES_BN_FOLD_MAX 8
+int es_bn_fold_batch(int n, const float* const* gamma, const float* const* beta, const float* const* running_mean,
+                     const float* const* running_var, const int* C, const float* eps, float* const* scale,
+                     float* const* shift, es_stream_t stream);
+/* Last pass of a routed simulation for one expert (train/utils.py:208-266: relu is the generator's
+ * last layer, np.expm1 of the prediction, `predictions[indices] = ...` scatter; train/utils.py:62-78
+ * channel sums).  x: the expert's pre-activation last-conv output [cap,1,H,W] fp32 (any strides); for
+ * i < min(live[0], cap) (live NULL: cap): v = relu(x[i]); image perm[start[0] + i] of the
+ * batch-ordered out [N,H,W] fp32 (dense) = v, or expm1(v) when photons != 0; sums[(perm[start[0] + i]) * 5
+ * .. + 4] (fp64) = the five masked sums of expm1(v), same masks and summation order as es_channel_sums
+ * with log_domain = 1.  out or sums may be NULL; perm NULL: identity (image i). */
+int es_sim_finish(const es_view_t* x, const void* xp, const int32_t* live, const int32_t* perm,
+                  const int32_t* start, int photons, float* out, double* sums, es_stream_t stream);
 
 #ifdef __cplusplus
 }
