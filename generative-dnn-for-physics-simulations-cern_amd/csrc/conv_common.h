@@ -73,8 +73,8 @@ struct ConvArgs {
   int bnr_dfirst, bnr_drop;
   float* bnr_part;              // [workgroup][3][Ng] (slots 1, 2: the two sums)
   int det;                      // WGRAD (es_conv2d_wgrad_det): split z stores its raw tile into
-                                // g_det_req.ws + z * M * Ng instead of atomics; split-K FWD / DGRAD
-                                // (es_conv2d_*_det): into det_ws + z * M * Ng
+                                // out (ConvCall::det_ws) + z * M * Ng instead of atomics; split-K FWD /
+                                // DGRAD (es_conv2d_*_det): into det_ws + z * M * Ng
   float* det_ws;
   int prio;                     // split-fp32 ring kernels: waves 4-7 at s_setprio 1 (VALU arbitration)
   int nbase;                    // dynamic rows: the launch's first image within d.rows' count (chunks)
@@ -114,69 +114,52 @@ __device__ __forceinline__ void conv_live_gemm(ConvArgs& a, int mode) {
 }
 
 
-// es_conv2d_wgrad_det: the partial buffer offered to the generic (register-staged / thin) WGRAD
-// kernels (host, per thread); the launch sets splits = partial slots written
-struct DetRequest {
-  float* ws;
-  int64_t floats;
-  int splits;
+// One call of a public conv entry (es_conv2d_*): what the caller asked for beyond the plain
+// convolution, and what the launch path answers.  Host only: it lives on the stack of the C-ABI entry
+// and is passed by reference down to the kernel launch.  A default-constructed value is a plain call.
+struct ConvCall {
+  // requests
+  float* stats_part = nullptr;        // es_conv2d_fwd_stats: BatchNorm partials of the output, [chunk][3][Ng]
+  int64_t stats_floats = 0;
+  const es_affine_t* aff = nullptr;   // es_conv2d_fwd_affine: y = act(scale[k] * (acc + bias[k]) + shift[k])
+  const void* bnr_x = nullptr;        // es_conv2d_dgrad_bnred: the consuming BatchNorm's input, statistics
+  const es_norm_t* bnr_nm = nullptr;  // and chain, and the buffer of its backward's partial sums
+  const es_chain_t* bnr_ch = nullptr;
+  float* bnr_part = nullptr;
+  int64_t bnr_floats = 0;
+  float* det_ws = nullptr;            // es_conv2d_*_det: workspace of per-split partials (ordered sums)
+  int64_t det_floats = 0;
+  // results
+  int stats_chunks = 0;   // partials a ring FWD launch wrote into stats_part (0: none)
+  int bnr_chunks = 0;     // partials a DGRAD launch wrote into bnr_part (0: the request was declined)
+  int det_splits = 0;     // partial slots written into det_ws (0: the kernel wrote the output itself)
+  int aff_fused = 0;      // the kernel that ran applied the affine epilogue
+  int path = 0;           // PATH_* bits of the kernels that ran (es_conv_exec_flops accounting)
 };
-extern thread_local DetRequest g_det_req;
+enum { PATH_RING = 1, PATH_SPLIT = 2, PATH_SUBPIXEL = 4, PATH_THIN = 8 };   // (SPLIT: split-fp32 planes)
 
-// es_conv2d_dgrad_bnred: the caller's request (host, per thread); the persistent DGRAD launch
-// sets chunks when it wrote the sums
-struct BnRedRequest {
-  const void* x;
-  const es_norm_t* nm;
-  const es_chain_t* ch;
-  float* part;
-  int64_t floats;
-  int chunks;
-};
-extern thread_local BnRedRequest g_bnr_req;
+// rows of a DGRAD over n images: the source grid when the integer upsample is folded into the GEMM
+inline int64_t dgrad_rows(const es_conv_desc_t& d, int n) {
+  return (int64_t)n * (d.up_h > 0 ? d.H * d.W : d.Hu * d.Wu);
+}
 
-
-
-// es_conv2d_fwd_stats: the caller's request for fused BatchNorm partials (host, per thread); the
-// ring FWD launch sets chunks when it writes them.
-struct StatsRequest {
-  float* part;
-  int64_t floats;
-  int chunks;
-};
-extern thread_local StatsRequest g_stats_req;
-
-// es_conv2d_fwd_affine: the caller's request (host, per thread); a ring FWD launch whose kernel
-// applies y = act(scale[k] * (acc + bias[k]) + shift[k]) before rounding sets fused.  Such a request
-// never comes with a StatsRequest.
-struct AffineRequest {
-  const float* scale;
-  const float* shift;
-  int act;
-  float slope;
-  int fused;
-};
-extern thread_local AffineRequest g_aff_req;
 // the fp32 MFMA arithmetic level of the ring kernels (es_conv_set_f32_split: 0 exact, 1 / 2 split-fp32)
 int es_f32_split_level();
-
-// which ring path the last conv launch took (host, per thread; es_conv_exec_flops accounting):
-// bit 0 a ring kernel ran, bit 1 split-fp32 planes, bit 2 the sub-pixel decomposition
-extern thread_local int g_ring_hit;
 
 // split-fp32 weight planes: byte offset of the planes behind an fp32 packing of n elements
 extern "C" int64_t es_weight_planes_offset(int64_t n);
 
 // 8-wave LDS-DMA ring kernels (conv_mfma.hip).  Return 1 when the call was launched, 0 when the
 // shape is not eligible (the caller falls back to the kernels of conv_igemm.hip), <0 on error.
-int es_conv_ring_launch(ConvArgs& a, int mode, hipStream_t st);
+int es_conv_ring_launch(ConvArgs& a, int mode, ConvCall& call, hipStream_t st);
 // fp32 operands (parity mode): FWD / DGRAD ring kernels over image chunks (same return convention)
-int es_conv_ring_launch_f32(ConvArgs& a, int mode, hipStream_t st);
+int es_conv_ring_launch_f32(ConvArgs& a, int mode, ConvCall& call, hipStream_t st);
 // deterministic fp32 WGRAD on the ring (conv_mfma.hip): partial floats needed (-1: not eligible), and
-// the launch (partials + ordered reduce into the torch-layout dW; 1 done, 0 not eligible, < 0 error)
+// the launch (partials in call.det_ws + ordered reduce into the torch-layout dW; 1 done, 0 not eligible,
+// < 0 error)
 int64_t es_wgrad_f32_ring_floats(const es_conv_desc_t& d, const int64_t ys[4], const int64_t xs[4]);
 int es_wgrad_f32_ring(const es_conv_desc_t& d, const void* dy, const int64_t ys[4], const void* x,
-                      const int64_t xs[4], float* dw, float beta, float* ws, int64_t ws_floats, hipStream_t st);
+                      const int64_t xs[4], float* dw, float beta, ConvCall& call, hipStream_t st);
 // the wave-specialised split-fp32 WGRAD partial kernel (conv_wgrad_ws.hip), 128 x bn tiles over grid
 // (row tiles, column tiles, K splits); 1 launched, 0 not eligible
 int es_wgrad_ws_launch(int bn, bool sp, dim3 grid, const ConvArgs& a, float* wsc, int ngt, hipStream_t st);

@@ -27,14 +27,15 @@
 
 #include "conv_common.h"
 
-// direct kernels for one-input-channel / one-output-channel convolutions (conv_thin.hip)
+// direct kernels for one-input-channel / one-output-channel convolutions (conv_thin.hip): 1 launched
+// (call.path gets PATH_THIN), 0 not a thin conv
 int es_thin_conv_fwd(const es_conv_desc_t* d, es_dtype_t dt, const void* x, const int64_t xs[4], const void* wk,
-                     const float* bias, void* y, es_dtype_t ydt, const int64_t ys[4], hipStream_t st);
+                     const float* bias, void* y, es_dtype_t ydt, const int64_t ys[4], ConvCall& call, hipStream_t st);
 int es_thin_conv_dgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, const int64_t ys[4],
                        const void* wd, void* dx, es_dtype_t dxdt, const int64_t dxs[4], float beta,
-                       hipStream_t st);
+                       ConvCall& call, hipStream_t st);
 int es_thin_conv_wgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, const int64_t ys[4], const void* x,
-                       const int64_t xs[4], float* dw, hipStream_t st);
+                       const int64_t xs[4], float* dw, ConvCall& call, hipStream_t st);
 
 namespace {
 
@@ -862,7 +863,7 @@ int launch_glds(ConvArgs& a, hipStream_t st) {
 }
 
 template <typename T, int MODE>
-int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
+int launch(ConvArgs& a, bool avec, bool bvec, ConvCall& call, hipStream_t st) {
   constexpr int BK = KSTEP_BYTES / sizeof(T);
   if constexpr (sizeof(T) == 2 && MODE != MODE_WGRAD) {
     // LDS-DMA path: one tap x 64 channels per K-step, big enough to fill the chip without split-K
@@ -871,13 +872,13 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
     const bool splitk_better = a.dense_f32_out && tiles < 256 && a.Kd / 64 >= 16;   // see below
     // (an affine-epilogue FWD, es_conv2d_fwd_affine, also takes the ring below 128 rows: its tiles pad
     // the rows, and only the ring kernels carry that epilogue)
-    const bool small_aff = MODE == MODE_FWD && a.M < 128 && g_aff_req.scale != nullptr;
+    const bool small_aff = MODE == MODE_FWD && a.M < 128 && call.aff != nullptr;
     if (avec && bvec && nch % 64 == 0 && a.d.stride <= 2 && a.d.hmap == nullptr && (a.M >= 128 || small_aff) &&
         !splitk_better && !g_no_glds) {
       a.k_per_split = a.Kd;
       a.splitk = 0;
       if (a.Kd % 64 == 0) {
-        const int rc = es_conv_ring_launch(a, MODE, st);
+        const int rc = es_conv_ring_launch(a, MODE, call, st);
         if (rc) {
           ES_CHECK_LAUNCH();
           return ES_OK;
@@ -896,12 +897,12 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
     // (the gathered grid's pixels per image: >= 8 keeps the row tiles' padding small; the aux
     // regressor's conv4 has a 1 x 15 output and a 3 x 17 input; linears take the pixel view)
     const int gpix = MODE == MODE_FWD ? a.d.P * a.d.Q : a.d.Hu * a.d.Wu;
-    const bool small_aff = MODE == MODE_FWD && a.M < 128 && g_aff_req.scale != nullptr && es_f32_split_level() > 0;
+    const bool small_aff = MODE == MODE_FWD && a.M < 128 && call.aff != nullptr && es_f32_split_level() > 0;
     if (avec && bvec && nch % 32 == 0 && a.Kd % 32 == 0 && a.d.stride <= 2 && a.d.hmap == nullptr &&
         gpix >= 8 && (a.M >= 128 || small_aff) && !g_no_glds) {
       a.k_per_split = a.Kd;
       a.splitk = 0;
-      const int rc = es_conv_ring_launch_f32(a, MODE, st);
+      const int rc = es_conv_ring_launch_f32(a, MODE, call, st);
       if (rc < 0) return ES_ERR_ARG;
       if (rc > 0) {
         ES_CHECK_LAUNCH();
@@ -914,7 +915,7 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
   const int tiles128 = ((a.M + 127) / 128) * ((a.Ng + 127) / 128);
   // (deterministic mode: only with a partial workspace, es_conv2d_fwd_det / es_conv2d_dgrad_det)
   const bool splitk_case = MODE != MODE_WGRAD && a.dense_f32_out && tiles128 < 256 && (a.Kd + BK - 1) / BK >= 16 &&
-                           !(sizeof(T) == 4 && g_es_det && g_det_req.ws == nullptr);
+                           !(sizeof(T) == 4 && g_es_det && call.det_ws == nullptr);
   // 128 x 128 only with enough tiles to fill the chip: a small GEMM (the discriminator / router /
   // aux linears at batch 512) is latency-bound per K-step, so more, smaller workgroups finish sooner
   const bool big = a.M >= 128 && a.Ng >= 96 && !splitk_case && tiles128 >= 128;
@@ -926,7 +927,7 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
   const int BM = big ? 128 : (narrow_n ? 128 : (narrow_m ? 32 : 64));
   const int BN = big ? 128 : (narrow_n ? 32 : (narrow_m ? 128 : 64));
   if constexpr (sizeof(T) == 2 && MODE == MODE_WGRAD) {
-    if (!a.det && avec && bvec && !g_no_glds && es_conv_ring_launch(a, MODE, st)) {
+    if (!a.det && avec && bvec && !g_no_glds && es_conv_ring_launch(a, MODE, call, st)) {
       ES_CHECK_LAUNCH();
       return ES_OK;
     }
@@ -955,18 +956,18 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
     want = max(1, min(want, ksteps / 4 > 0 ? ksteps / 4 : 1));  // >= 4 K-steps per split
     if (a.det) {   // deterministic: one partial slot per split, within the caller's workspace
       const int64_t slot = (int64_t)a.M * a.Ng;
-      want = (int)std::max<int64_t>(1, std::min<int64_t>(want, g_det_req.floats / slot));
+      want = (int)std::max<int64_t>(1, std::min<int64_t>(want, call.det_floats / slot));
     }
     const int per = ((ksteps + want - 1) / want) * BK;
     a.k_per_split = per;
     splits = (a.Kd + per - 1) / per;
-    if (a.det) g_det_req.splits = splits;
+    if (a.det) call.det_splits = splits;
   } else if (splitk_case) {
     // few output tiles and a long K (the linears at batch 512): split K over ~1024 workgroups,
     // at least 4 K-steps each
     int want = min((1024 + tiles - 1) / tiles, ksteps / 4);
-    const bool det = g_det_req.ws != nullptr;
-    if (det) want = (int)std::min<int64_t>(want, g_det_req.floats / ((int64_t)a.M * a.Ng));
+    const bool det = call.det_ws != nullptr;
+    if (det) want = (int)std::min<int64_t>(want, call.det_floats / ((int64_t)a.M * a.Ng));
     if (want > 1) {
       const int per = ((ksteps + want - 1) / want) * BK;
       a.k_per_split = per;
@@ -974,8 +975,8 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
       a.splitk = splits > 1;
       if (det && a.splitk) {   // ordered: split z stores into its own slot, es_splitk_reduce sums
         a.det = 1;
-        a.det_ws = g_det_req.ws;
-        g_det_req.splits = splits;
+        a.det_ws = call.det_ws;
+        call.det_splits = splits;
       } else if (a.splitk && hipMemsetAsync(a.out, 0, (size_t)a.M * a.Ng * sizeof(float), st) != hipSuccess) {
         es_set_error("conv: split-K memset failed");
         return ES_ERR_HIP;
@@ -993,18 +994,25 @@ int launch(ConvArgs& a, bool avec, bool bvec, hipStream_t st) {
   return launch_tile<T, MODE, 64, 64>(a, avec, bvec, st, splits);
 }
 
-template <int MODE>
-int dispatch(ConvArgs& a, es_dtype_t dt, bool avec, bool bvec, hipStream_t st) {
+void fill_divs(ConvArgs& a) {
   a.fC = mkdiv(a.d.C); a.fS = mkdiv(a.d.S); a.fK = mkdiv(a.d.K); a.fQ = mkdiv(a.d.Q);
   a.fP = mkdiv(a.d.P); a.fWu = mkdiv(a.d.Wu); a.fHu = mkdiv(a.d.Hu);
   a.fUh = mkdiv(a.d.up_h > 0 ? a.d.up_h : 1); a.fUw = mkdiv(a.d.up_w > 0 ? a.d.up_w : 1);
   a.fRSK = mkdiv(a.d.R * a.d.S * a.d.K); a.fW = mkdiv(a.d.W); a.fH = mkdiv(a.d.H);
+}
+
+template <int MODE>
+int dispatch(ConvArgs& a, es_dtype_t dt, bool avec, bool bvec, ConvCall& call, hipStream_t st) {
+  fill_divs(a);
   if (a.d.stride > 2) avec = bvec = false;   // vector DGRAD gather handles strides 1 and 2
-  if (dt == ES_F32) return launch<float, MODE>(a, avec, bvec, st);
-  if (dt == ES_BF16) return launch<bf16, MODE>(a, avec, bvec, st);
+  if (dt == ES_F32) return launch<float, MODE>(a, avec, bvec, call, st);
+  if (dt == ES_BF16) return launch<bf16, MODE>(a, avec, bvec, call, st);
   es_set_error("conv: unsupported dtype %d", (int)dt);
   return ES_ERR_ARG;
 }
+
+// 16-byte vector access along an operand dimension of n values with element stride `stride`
+bool vec16(es_dtype_t dt, int64_t stride, int n) { return stride == 1 && n % (dt == ES_BF16 ? 8 : 4) == 0; }
 
 // strides (n, c, h, w) describe a dense [n][h][w][c] tensor (rows of c contiguous values)
 bool dense_rows(const int64_t s[4], int c, int h, int w) {
@@ -1029,48 +1037,90 @@ int check_desc(const es_conv_desc_t* d) {
 }
 
 // sub-pixel FWD / DGRAD: only the ring kernels read mode 2 / 3 packed weights
-int ring_direct(ConvArgs& a, int mode, hipStream_t st, es_dtype_t dt) {
-  a.fC = mkdiv(a.d.C); a.fS = mkdiv(a.d.S); a.fK = mkdiv(a.d.K); a.fQ = mkdiv(a.d.Q);
-  a.fP = mkdiv(a.d.P); a.fWu = mkdiv(a.d.Wu); a.fHu = mkdiv(a.d.Hu);
-  a.fUh = mkdiv(2); a.fUw = mkdiv(2);
-  a.fRSK = mkdiv(a.d.R * a.d.S * a.d.K); a.fW = mkdiv(a.d.W); a.fH = mkdiv(a.d.H);
+int ring_direct(ConvArgs& a, int mode, es_dtype_t dt, ConvCall& call, hipStream_t st) {
+  fill_divs(a);
   a.k_per_split = a.Kd;
   a.splitk = 0;
-  const int rc = dt == ES_F32 ? es_conv_ring_launch_f32(a, mode, st) : es_conv_ring_launch(a, mode, st);
+  const int rc = dt == ES_F32 ? es_conv_ring_launch_f32(a, mode, call, st) : es_conv_ring_launch(a, mode, call, st);
   ES_CHECK_ARG(rc > 0, "conv: sub-pixel operands not dense NHWC (ring kernels required)");
   ES_CHECK_LAUNCH();
   return ES_OK;
 }
 
-}  // namespace
-
 // ---------------------------------------------------------------- executed-work tally (es_conv_exec_flops)
-thread_local int g_ring_hit = 0;
-namespace {
 // per host thread (the probe reads the thread that issued the convs)
 thread_local double g_exec_flops[3] = {0.0, 0.0, 0.0};
-// RAII around one conv entry: classifies the path the call took and adds its executed FLOPs, only
-// when the entry returns ES_OK (ok() marks it: failed calls issue no work)
-struct ExecTally {
-  const es_conv_desc_t* d;
-  es_dtype_t dt;
-  bool thin = false;
-  bool done = false;
-  ExecTally(const es_conv_desc_t* d_, es_dtype_t dt_) : d(d_), dt(dt_) { g_ring_hit = 0; }
-  int ok(int rc) {
-    done = rc == ES_OK;
-    return rc;
+// Ends one conv entry: classifies the path the call took (call.path) and adds its executed FLOPs,
+// only when the entry succeeded (failed calls issue no work).  Returns rc.
+int tally(const es_conv_desc_t* d, es_dtype_t dt, const ConvCall& call, int rc) {
+  if (rc != ES_OK) return rc;
+  double f = 2.0 * d->N * d->P * d->Q * (double)d->K * d->C * d->R * d->S;
+  if (call.path & PATH_SUBPIXEL) f *= (double)es_subpixel_taps(d->R, d->S) / (4.0 * d->R * d->S);
+  if (call.path & PATH_THIN) g_exec_flops[2] += f;
+  else if (dt == ES_BF16) g_exec_flops[0] += f;
+  else if (call.path & PATH_SPLIT) g_exec_flops[0] += 6.0 * f;
+  else g_exec_flops[1] += f;
+  return rc;
+}
+
+// ------------------------------------------------------------ the three convolutions, per call context
+int conv_fwd(const es_conv_desc_t* d, es_dtype_t dt, const void* x, const int64_t xs[4], const void* wk,
+             const float* bias, void* y, es_dtype_t ydt, const int64_t ys[4], ConvCall& call, hipStream_t st) {
+  if (int e = check_desc(d)) return e;
+  if (d->subpixel) ES_CHECK_ARG(es_conv_subpixel_ok(d, dt), "conv fwd: sub-pixel weights for a conv the sub-pixel path cannot run");
+  if (es_thin_conv_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, call, st)) {
+    ES_CHECK_LAUNCH();
+    return ES_OK;
   }
-  ~ExecTally() {
-    if (!d || !done) return;
-    double f = 2.0 * d->N * d->P * d->Q * (double)d->K * d->C * d->R * d->S;
-    if (g_ring_hit & 4) f *= (double)es_subpixel_taps(d->R, d->S) / (4.0 * d->R * d->S);
-    if (thin) g_exec_flops[2] += f;
-    else if (dt == ES_BF16) g_exec_flops[0] += f;
-    else if (g_ring_hit & 2) g_exec_flops[0] += 6.0 * f;
-    else g_exec_flops[1] += f;
+  ConvArgs a{};
+  a.d = *d; a.a_src = x; a.b_src = wk; a.out = y; a.bias = bias; a.beta = 0.f;
+  a.out_bf16 = ydt == ES_BF16;
+  for (int i = 0; i < 4; ++i) { a.as[i] = xs[i]; a.os[i] = ys[i]; }
+  a.M = d->N * d->P * d->Q; a.Ng = d->K; a.Kd = d->R * d->S * d->C;
+  a.dense_f32_out = ydt == ES_F32 && dense_rows(ys, d->K, d->P, d->Q);
+  if (d->subpixel) return ring_direct(a, MODE_FWD, dt, call, st);
+  return dispatch<MODE_FWD>(a, dt, vec16(dt, xs[1], d->C), vec16(dt, 1, a.Kd), call, st);
+}
+
+int conv_dgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, const int64_t ys[4], const void* wd,
+               void* dxu, es_dtype_t dxdt, const int64_t dxs[4], float beta, ConvCall& call, hipStream_t st) {
+  if (int e = check_desc(d)) return e;
+  if (d->subpixel) ES_CHECK_ARG(es_conv_subpixel_ok(d, dt), "conv dgrad: sub-pixel weights for a conv the sub-pixel path cannot run");
+  if (es_thin_conv_dgrad(d, dt, dy, ys, wd, dxu, dxdt, dxs, beta, call, st)) {
+    ES_CHECK_LAUNCH();
+    return ES_OK;
   }
-};
+  ConvArgs a{};
+  a.d = *d; a.a_src = dy; a.b_src = wd; a.out = dxu; a.bias = nullptr; a.beta = beta;
+  a.out_bf16 = dxdt == ES_BF16;
+  for (int i = 0; i < 4; ++i) { a.as[i] = ys[i]; a.os[i] = dxs[i]; }
+  a.fold = d->up_h > 0;
+  a.M = (int)dgrad_rows(*d, d->N); a.Ng = d->C;
+  a.Kd = (a.fold ? d->up_h * d->up_w : 1) * d->R * d->S * d->K;
+  a.dense_f32_out = dxdt == ES_F32 && beta == 0.f &&
+                    dense_rows(dxs, d->C, a.fold ? d->H : d->Hu, a.fold ? d->W : d->Wu);
+  if (d->subpixel) return ring_direct(a, MODE_DGRAD, dt, call, st);
+  return dispatch<MODE_DGRAD>(a, dt, vec16(dt, ys[1], d->K), vec16(dt, 1, a.Kd), call, st);
+}
+
+// dw += the weight gradient (packed layout, float atomics); with a deterministic workspace
+// (call.det_ws) the call.det_splits raw per-split partials go there instead and the caller reduces them
+int conv_wgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, const int64_t ys[4], const void* x,
+               const int64_t xs[4], float* dw, ConvCall& call, hipStream_t st) {
+  if (int e = check_desc(d)) return e;
+  float* out = call.det_ws ? call.det_ws : dw;
+  if (es_thin_conv_wgrad(d, dt, dy, ys, x, xs, out, call, st)) {
+    ES_CHECK_LAUNCH();
+    return ES_OK;
+  }
+  ConvArgs a{};
+  a.d = *d; a.a_src = dy; a.b_src = x; a.out = out;
+  for (int i = 0; i < 4; ++i) { a.as[i] = ys[i]; a.bs[i] = xs[i]; }
+  a.M = d->K; a.Ng = d->R * d->S * d->C; a.Kd = d->N * d->P * d->Q;
+  a.det = call.det_ws != nullptr;
+  return dispatch<MODE_WGRAD>(a, dt, vec16(dt, ys[1], d->K), vec16(dt, xs[1], d->C), call, st);
+}
+
 }  // namespace
 
 extern "C" int es_conv_exec_flops(double out[3], int reset) {
@@ -1097,35 +1147,19 @@ extern "C" int es_conv_set_glds(int on) {
 extern "C" int es_conv2d_fwd(const es_conv_desc_t* d, es_dtype_t dt, const void* x,
                              const int64_t xs[4], const void* wk, const float* bias, void* y,
                              es_dtype_t ydt, const int64_t ys[4], es_stream_t stream) {
-  if (int e = check_desc(d)) return e;
-  ExecTally tally(d, dt);
-  if (d->subpixel) ES_CHECK_ARG(es_conv_subpixel_ok(d, dt), "conv fwd: sub-pixel weights for a conv the sub-pixel path cannot run");
-  if (es_thin_conv_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, (hipStream_t)stream)) {
-    tally.thin = true;
-    ES_CHECK_LAUNCH();
-    return tally.ok(ES_OK);
-  }
-  ConvArgs a{};
-  a.d = *d; a.a_src = x; a.b_src = wk; a.out = y; a.bias = bias; a.beta = 0.f;
-  a.out_bf16 = ydt == ES_BF16;
-  for (int i = 0; i < 4; ++i) { a.as[i] = xs[i]; a.os[i] = ys[i]; }
-  a.M = d->N * d->P * d->Q; a.Ng = d->K; a.Kd = d->R * d->S * d->C;
-  a.dense_f32_out = ydt == ES_F32 && dense_rows(ys, d->K, d->P, d->Q);
-  const int vn = dt == ES_BF16 ? 8 : 4;
-  const bool avec = xs[1] == 1 && d->C % vn == 0;
-  const bool bvec = a.Kd % vn == 0;
-  if (d->subpixel) return tally.ok(ring_direct(a, MODE_FWD, (hipStream_t)stream, dt));
-  return tally.ok(dispatch<MODE_FWD>(a, dt, avec, bvec, (hipStream_t)stream));
+  ConvCall call;
+  return tally(d, dt, call, conv_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, call, (hipStream_t)stream));
 }
 
 extern "C" int es_conv2d_fwd_stats(const es_conv_desc_t* d, es_dtype_t dt, const void* x, const int64_t xs[4],
                                    const void* wk, const float* bias, void* y, es_dtype_t ydt, const int64_t ys[4],
                                    float* part, int64_t part_floats, int* chunks, es_stream_t stream) {
   ES_CHECK_ARG(part && chunks, "conv fwd stats: part / chunks NULL");
-  g_stats_req = StatsRequest{part, part_floats, 0};
-  const int rc = es_conv2d_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, stream);
-  *chunks = g_stats_req.chunks;
-  g_stats_req = StatsRequest{nullptr, 0, 0};
+  ConvCall call;
+  call.stats_part = part;
+  call.stats_floats = part_floats;
+  const int rc = tally(d, dt, call, conv_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, call, (hipStream_t)stream));
+  *chunks = call.stats_chunks;
   return rc;
 }
 
@@ -1138,41 +1172,18 @@ extern "C" int es_conv2d_fwd_affine(const es_conv_desc_t* d, es_dtype_t dt, cons
   ES_CHECK_ARG(epi && epi->scale && epi->shift && fused, "conv fwd affine: epi / scale / shift / fused NULL");
   ES_CHECK_ARG(epi->act == ES_ACT_NONE || epi->act == ES_ACT_RELU || epi->act == ES_ACT_LRELU,
                "conv fwd affine: unknown activation %d", epi->act);
-  g_aff_req = AffineRequest{epi->scale, epi->shift, epi->act, epi->slope, 0};
-  const int rc = es_conv2d_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, stream);
-  *fused = rc == ES_OK ? g_aff_req.fused : 0;
-  g_aff_req = AffineRequest{nullptr, nullptr, 0, 0.f, 0};
+  ConvCall call;
+  call.aff = epi;
+  const int rc = tally(d, dt, call, conv_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, call, (hipStream_t)stream));
+  *fused = rc == ES_OK ? call.aff_fused : 0;
   return rc;
 }
 
 extern "C" int es_conv2d_dgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy,
                                const int64_t ys[4], const void* wd, void* dxu, es_dtype_t dxdt,
                                const int64_t dxs[4], float beta, es_stream_t stream) {
-  if (int e = check_desc(d)) return e;
-  ExecTally tally(d, dt);
-  if (d->subpixel) ES_CHECK_ARG(es_conv_subpixel_ok(d, dt), "conv dgrad: sub-pixel weights for a conv the sub-pixel path cannot run");
-  if (es_thin_conv_dgrad(d, dt, dy, ys, wd, dxu, dxdt, dxs, beta, (hipStream_t)stream)) {
-    tally.thin = true;
-    ES_CHECK_LAUNCH();
-    return tally.ok(ES_OK);
-  }
-  ConvArgs a{};
-  a.d = *d; a.a_src = dy; a.b_src = wd; a.out = dxu; a.bias = nullptr; a.beta = beta;
-  a.out_bf16 = dxdt == ES_BF16;
-  for (int i = 0; i < 4; ++i) { a.as[i] = ys[i]; a.os[i] = dxs[i]; }
-  a.fold = d->up_h > 0;
-  if (a.fold) { a.M = d->N * d->H * d->W; a.Kd = d->up_h * d->up_w * d->R * d->S * d->K; }
-  else { a.M = d->N * d->Hu * d->Wu; a.Kd = d->R * d->S * d->K; }
-  a.Ng = d->C;
-  {
-    const int64_t oh = a.fold ? d->H : d->Hu, ow = a.fold ? d->W : d->Wu;
-    a.dense_f32_out = dxdt == ES_F32 && beta == 0.f && dense_rows(dxs, d->C, (int)oh, (int)ow);
-  }
-  const int vn = dt == ES_BF16 ? 8 : 4;
-  const bool avec = ys[1] == 1 && d->K % vn == 0;
-  const bool bvec = a.Kd % vn == 0;
-  if (d->subpixel) return tally.ok(ring_direct(a, MODE_DGRAD, (hipStream_t)stream, dt));
-  return tally.ok(dispatch<MODE_DGRAD>(a, dt, avec, bvec, (hipStream_t)stream));
+  ConvCall call;
+  return tally(d, dt, call, conv_dgrad(d, dt, dy, ys, wd, dxu, dxdt, dxs, beta, call, (hipStream_t)stream));
 }
 
 extern "C" int es_conv2d_dgrad_bnred(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, const int64_t ys[4],
@@ -1180,31 +1191,20 @@ extern "C" int es_conv2d_dgrad_bnred(const es_conv_desc_t* d, es_dtype_t dt, con
                                      const void* x, const es_norm_t* nm, const es_chain_t* ch, float* part,
                                      int64_t part_floats, int* chunks, es_stream_t stream) {
   ES_CHECK_ARG(part && chunks && x && nm && ch, "conv dgrad bnred: NULL argument");
-  g_bnr_req = BnRedRequest{x, nm, ch, part, part_floats, 0};
-  const int rc = es_conv2d_dgrad(d, dt, dy, ys, wd, dx, dxdt, dxs, 0.f, stream);
-  *chunks = g_bnr_req.chunks;
-  g_bnr_req = BnRedRequest{nullptr, nullptr, nullptr, nullptr, 0, 0};
+  ConvCall call;
+  call.bnr_x = x; call.bnr_nm = nm; call.bnr_ch = ch;
+  call.bnr_part = part;
+  call.bnr_floats = part_floats;
+  const int rc = tally(d, dt, call, conv_dgrad(d, dt, dy, ys, wd, dx, dxdt, dxs, 0.f, call, (hipStream_t)stream));
+  *chunks = call.bnr_chunks;
   return rc;
 }
 
 extern "C" int es_conv2d_wgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy,
                                const int64_t ys[4], const void* x, const int64_t xs[4], float* dw,
                                es_stream_t stream) {
-  if (int e = check_desc(d)) return e;
-  ExecTally tally(d, dt);
-  if (es_thin_conv_wgrad(d, dt, dy, ys, x, xs, dw, (hipStream_t)stream)) {
-    tally.thin = true;
-    ES_CHECK_LAUNCH();
-    return tally.ok(ES_OK);
-  }
-  ConvArgs a{};
-  a.d = *d; a.a_src = dy; a.b_src = x; a.out = dw;
-  for (int i = 0; i < 4; ++i) { a.as[i] = ys[i]; a.bs[i] = xs[i]; }
-  a.M = d->K; a.Ng = d->R * d->S * d->C; a.Kd = d->N * d->P * d->Q;
-  const int vn = dt == ES_BF16 ? 8 : 4;
-  const bool avec = ys[1] == 1 && d->K % vn == 0;
-  const bool bvec = xs[1] == 1 && d->C % vn == 0;
-  return tally.ok(dispatch<MODE_WGRAD>(a, dt, avec, bvec, (hipStream_t)stream));
+  ConvCall call;
+  return tally(d, dt, call, conv_wgrad(d, dt, dy, ys, x, xs, dw, call, (hipStream_t)stream));
 }
 
 // ------------------------------------------------------------------------- deterministic WGRAD
@@ -1212,7 +1212,6 @@ extern "C" int es_conv2d_wgrad(const es_conv_desc_t* d, es_dtype_t dt, const voi
 // a fixed summation order: the K splits store raw partials into the caller's workspace (no float
 // atomics) and one ordered reduce sums them.  fp32 shapes the ring takes run wgrad_f32_kernel
 // (conv_mfma.hip); the rest run the register-staged / thin kernels with per-split partials.
-thread_local DetRequest g_det_req;
 bool g_es_det = false;
 
 namespace {
@@ -1221,6 +1220,13 @@ namespace {
 int64_t generic_det_floats(const es_conv_desc_t* d) {
   const int64_t per = (int64_t)d->K * d->R * d->S * d->C;
   return per * std::max<int64_t>(8, std::min<int64_t>(2048, (1ll << 26) / per));
+}
+
+ConvCall det_call(void* ws, int64_t ws_bytes) {
+  ConvCall call;
+  call.det_ws = (float*)ws;
+  call.det_floats = ws_bytes / (int64_t)sizeof(float);
+  return call;
 }
 }  // namespace
 
@@ -1238,40 +1244,22 @@ extern "C" int es_conv2d_wgrad_det(const es_conv_desc_t* d, es_dtype_t dt, const
                                    int64_t ws_bytes, es_stream_t stream) {
   if (int e = check_desc(d)) return e;
   ES_CHECK_ARG(dw && ws, "conv wgrad det: NULL dw / workspace");
-  ExecTally tally(d, dt);
   const hipStream_t st = (hipStream_t)stream;
-  const int64_t floats = ws_bytes / (int64_t)sizeof(float);
+  ConvCall call = det_call(ws, ws_bytes);
   if (dt == ES_F32) {
-    const int rc = es_wgrad_f32_ring(*d, dy, ys, x, xs, dw, beta, (float*)ws, floats, st);
+    const int rc = es_wgrad_f32_ring(*d, dy, ys, x, xs, dw, beta, call, st);
     if (rc < 0) return ES_ERR_ARG;
     if (rc > 0) {
       ES_CHECK_LAUNCH();
-      return tally.ok(ES_OK);
+      return tally(d, dt, call, ES_OK);
     }
   }
-  const int64_t per = (int64_t)d->K * d->R * d->S * d->C;
-  ES_CHECK_ARG(floats >= per, "conv wgrad det: workspace below one partial");
-  g_det_req = DetRequest{(float*)ws, floats, 0};
-  int rc = es_thin_conv_wgrad(d, dt, dy, ys, x, xs, (float*)ws, st) ? ES_OK : -1;
-  tally.thin = rc == ES_OK;
-  if (rc != ES_OK) {
-    ConvArgs a{};
-    a.d = *d; a.a_src = dy; a.b_src = x; a.out = ws;
-    for (int i = 0; i < 4; ++i) { a.as[i] = ys[i]; a.bs[i] = xs[i]; }
-    a.M = d->K; a.Ng = d->R * d->S * d->C; a.Kd = d->N * d->P * d->Q;
-    const int vn = dt == ES_BF16 ? 8 : 4;
-    const bool avec = ys[1] == 1 && d->K % vn == 0;
-    const bool bvec = xs[1] == 1 && d->C % vn == 0;
-    a.det = 1;
-    rc = dispatch<MODE_WGRAD>(a, dt, avec, bvec, st);
-  }
-  const int splits = g_det_req.splits;
-  g_det_req = DetRequest{nullptr, 0, 0};
-  if (rc != ES_OK) return rc;
-  ES_CHECK_ARG(splits > 0, "conv wgrad det: no partials written");
-  es_wgrad_reduce_plain((const float*)ws, splits, d->K, d->C, d->R, d->S, dw, beta, st);
+  ES_CHECK_ARG(call.det_floats >= (int64_t)d->K * d->R * d->S * d->C, "conv wgrad det: workspace below one partial");
+  if (int rc = conv_wgrad(d, dt, dy, ys, x, xs, dw, call, st)) return rc;
+  ES_CHECK_ARG(call.det_splits > 0, "conv wgrad det: no partials written");
+  es_wgrad_reduce_plain(call.det_ws, call.det_splits, d->K, d->C, d->R, d->S, dw, beta, st);
   ES_CHECK_LAUNCH();
-  return tally.ok(ES_OK);
+  return tally(d, dt, call, ES_OK);
 }
 
 // deterministic split-K FWD / DGRAD (the fp32 linears with few output tiles and a long K: the
@@ -1285,13 +1273,10 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int splits, i
     out[i] = v;
   }
 }
-int splitk_det_finish(int rc, float* out, int64_t n, hipStream_t st) {
-  const int splits = g_det_req.splits;
-  const float* ws = g_det_req.ws;
-  g_det_req = DetRequest{nullptr, 0, 0};
-  if (rc != ES_OK || splits == 0) return rc;   // no split: the kernel wrote out itself
+int splitk_det_finish(const ConvCall& call, float* out, int64_t n, hipStream_t st) {
+  if (call.det_splits == 0) return ES_OK;   // no split: the kernel wrote out itself
   const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, splits, n, out);
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, call.det_ws, call.det_splits, n, out);
   ES_CHECK_LAUNCH();
   return ES_OK;
 }
@@ -1299,8 +1284,7 @@ int splitk_det_finish(int rc, float* out, int64_t n, hipStream_t st) {
 
 extern "C" int64_t es_conv2d_splitk_ws_bytes(const es_conv_desc_t* d, int mode) {
   if (!d || check_desc(d) || (mode != MODE_FWD && mode != MODE_DGRAD)) return -1;
-  const int64_t M = mode == MODE_FWD ? (int64_t)d->N * d->P * d->Q
-                                     : (d->up_h > 0 ? (int64_t)d->N * d->H * d->W : (int64_t)d->N * d->Hu * d->Wu);
+  const int64_t M = mode == MODE_FWD ? (int64_t)d->N * d->P * d->Q : dgrad_rows(*d, d->N);
   const int64_t Ng = mode == MODE_FWD ? d->K : d->C;
   return M * Ng * kDetSplitK * (int64_t)sizeof(float);
 }
@@ -1309,19 +1293,20 @@ extern "C" int es_conv2d_fwd_det(const es_conv_desc_t* d, es_dtype_t dt, const v
                                  const void* wk, const float* bias, void* y, es_dtype_t ydt, const int64_t ys[4],
                                  void* ws, int64_t ws_bytes, es_stream_t stream) {
   ES_CHECK_ARG(ws, "conv fwd det: NULL workspace");
-  g_det_req = DetRequest{(float*)ws, ws_bytes / (int64_t)sizeof(float), 0};
-  const int rc = es_conv2d_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, stream);
-  return splitk_det_finish(rc, (float*)y, (int64_t)d->N * d->P * d->Q * d->K, (hipStream_t)stream);
+  ConvCall call = det_call(ws, ws_bytes);
+  const int rc = tally(d, dt, call, conv_fwd(d, dt, x, xs, wk, bias, y, ydt, ys, call, (hipStream_t)stream));
+  if (rc != ES_OK) return rc;
+  return splitk_det_finish(call, (float*)y, (int64_t)d->N * d->P * d->Q * d->K, (hipStream_t)stream);
 }
 
 extern "C" int es_conv2d_dgrad_det(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, const int64_t ys[4],
                                    const void* wd, void* dxu, es_dtype_t dxdt, const int64_t dxs[4], void* ws,
                                    int64_t ws_bytes, es_stream_t stream) {
   ES_CHECK_ARG(ws, "conv dgrad det: NULL workspace");
-  g_det_req = DetRequest{(float*)ws, ws_bytes / (int64_t)sizeof(float), 0};
-  const int rc = es_conv2d_dgrad(d, dt, dy, ys, wd, dxu, dxdt, dxs, 0.f, stream);
-  const int64_t M = d->up_h > 0 ? (int64_t)d->N * d->H * d->W : (int64_t)d->N * d->Hu * d->Wu;
-  return splitk_det_finish(rc, (float*)dxu, M * d->C, (hipStream_t)stream);
+  ConvCall call = det_call(ws, ws_bytes);
+  const int rc = tally(d, dt, call, conv_dgrad(d, dt, dy, ys, wd, dxu, dxdt, dxs, 0.f, call, (hipStream_t)stream));
+  if (rc != ES_OK) return rc;
+  return splitk_det_finish(call, (float*)dxu, dgrad_rows(*d, d->N) * d->C, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------- weight (un)packing

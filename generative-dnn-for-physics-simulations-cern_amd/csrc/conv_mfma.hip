@@ -2790,13 +2790,14 @@ static void launch_wgrad_reduce(const float* ws, int splits, int K, int C, int R
 int64_t g_conv_launches = 0;
 extern "C" int64_t es_conv_launch_count() { return g_conv_launches; }
 
-// One ring launch; aff (FWD, bf16 or split-fp32 operands): the instantiation with the affine +
-// activation epilogue (es_conv2d_fwd_affine), which reports itself in g_aff_req.fused.
+// One ring launch; with an affine + activation epilogue in the arguments (a.epi_scale: ring_fd sets it
+// for FWD with bf16 or split-fp32 operands, es_conv2d_fwd_affine) the instantiation that applies it,
+// which reports itself in call.aff_fused.
 template <int MODE, int BM, int BN, bool SP, int BK, typename T, int SPL>
-void launch_ring_grid(const ConvArgs& a, dim3 grid, hipStream_t st, bool aff) {
+void launch_ring_grid(const ConvArgs& a, dim3 grid, ConvCall& call, hipStream_t st) {
   if constexpr (MODE == MODE_FWD && (sizeof(T) == 2 || SPL > 0)) {
-    if (aff) {
-      g_aff_req.fused = 1;
+    if (a.epi_scale) {
+      call.aff_fused = 1;
       hipLaunchKernelGGL((conv_ring_kernel<MODE, BM, BN, SP, BK, T, SPL, true>), grid, dim3(RT), 0, st, a);
       return;
     }
@@ -2805,10 +2806,10 @@ void launch_ring_grid(const ConvArgs& a, dim3 grid, hipStream_t st, bool aff) {
 }
 
 template <int MODE, int BM, int BN, bool SP, int BK = 64, typename T = bf16, int SPL = 0>
-void launch_ring(const ConvArgs& a, int row_tiles, hipStream_t st, bool aff = false) {
+void launch_ring(const ConvArgs& a, int row_tiles, ConvCall& call, hipStream_t st) {
   dim3 grid(row_tiles, (a.Ng + BN - 1) / BN, 1);
   ++g_conv_launches;
-  launch_ring_grid<MODE, BM, BN, SP, BK, T, SPL>(a, grid, st, aff);
+  launch_ring_grid<MODE, BM, BN, SP, BK, T, SPL>(a, grid, call, st);
 }
 
 // minimum K-steps per WGRAD K-split (each split flushes its whole fp32 tile with atomics; 8 / 32 / 64
@@ -2862,10 +2863,6 @@ bool g_persist = true;
 bool g_p256 = true;
 
 }  // namespace
-
-thread_local StatsRequest g_stats_req;
-thread_local AffineRequest g_aff_req;
-thread_local BnRedRequest g_bnr_req;
 
 // Class geometry of the sub-pixel decomposition (see SubPixel): output row p belongs to class
 // a = (p - pad) mod 2, p = p0 + 2u, source row of combined tap d = u + oh + d, dh = taps.
@@ -2958,13 +2955,13 @@ extern "C" int es_conv_subpixel_ok(const es_conv_desc_t* d, es_dtype_t dt) {
 }
 
 template <typename T, int SPL = 0>
-int ring_fd(ConvArgs& a, int mode, hipStream_t st);
+int ring_fd(ConvArgs& a, int mode, ConvCall& call, hipStream_t st);
 namespace {
 int chunk_images(int64_t img_bytes, int N);
-int ring_launch_chunks(ConvArgs& a, int mode, int nc, hipStream_t st);
+int ring_launch_chunks(ConvArgs& a, int mode, int nc, int eb, ConvCall& call, hipStream_t st);
 }  // namespace
 
-int es_conv_ring_launch(ConvArgs& a, int mode, hipStream_t st) {
+int es_conv_ring_launch(ConvArgs& a, int mode, ConvCall& call, hipStream_t st) {
   const es_conv_desc_t& d = a.d;
   const bool sp_weights = d.subpixel != 0;   // FWD / DGRAD operands packed for the sub-pixel path
   if (g_ring_off && !sp_weights) return 0;
@@ -2974,7 +2971,7 @@ int es_conv_ring_launch(ConvArgs& a, int mode, hipStream_t st) {
   {
     const int64_t img = (mode == MODE_WGRAD ? std::max<int64_t>(a.as[0], a.bs[0]) : a.as[0]) * 2;
     const int nc = chunk_images(img, d.N);
-    if (nc < d.N) return ring_launch_chunks(a, mode, nc, st);
+    if (nc < d.N) return ring_launch_chunks(a, mode, nc, 2, call, st);
   }
   if (mode == MODE_WGRAD) {
     if (!dense_small(a.as, d.N, d.K, d.P, d.Q) || !dense_small(a.bs, d.N, d.C, d.H, d.W)) return 0;
@@ -2987,18 +2984,18 @@ int es_conv_ring_launch(ConvArgs& a, int mode, hipStream_t st) {
     else if (d.K == 64 && d.C % 128 == 0) ES_WG(64, 128);   // neutron G conv_layers.9 (128 -> 64)
     else return 0;
 #undef ES_WG
-    g_ring_hit = 1 | (sp ? 4 : 0);
+    call.path |= PATH_RING | (sp ? PATH_SUBPIXEL : 0);
     return 1;
   }
-  const int rc = ring_fd<bf16>(a, mode, st);
-  if (rc > 0) g_ring_hit = 1 | (sp_weights ? 4 : 0);
+  const int rc = ring_fd<bf16>(a, mode, call, st);
+  if (rc > 0) call.path |= PATH_RING | (sp_weights ? PATH_SUBPIXEL : 0);
   return rc;
 }
 
 // FWD / DGRAD ring launch for bf16 or fp32 operands (fp32: the parity mode's exact fp32 MFMA, or with
 // SPL the split-fp32 bf16-plane MFMA on 32-channel K-steps; the persistent kernels are bf16-only)
 template <typename T, int SPL>
-int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
+int ring_fd(ConvArgs& a, int mode, ConvCall& call, hipStream_t st) {
   const es_conv_desc_t& d = a.d;
   const bool sp_weights = d.subpixel != 0;
   if constexpr (SPL == 2) {   // the pre-split B planes follow the fp32 packing (es_pack_weight_planes)
@@ -3008,13 +3005,19 @@ int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
   constexpr int EB = sizeof(T);
   // affine + activation epilogue requested (es_conv2d_fwd_affine): bf16 and split-fp32 FWD kernels
   // carry it; the exact-fp32 ring does not (the caller then runs the norm pass)
-  const bool aff = mode == MODE_FWD && g_aff_req.scale != nullptr && (EB == 2 || SPL > 0);
+  const bool aff = mode == MODE_FWD && call.aff != nullptr && (EB == 2 || SPL > 0);
   if (aff) {
-    a.epi_scale = g_aff_req.scale;
-    a.epi_shift = g_aff_req.shift;
-    a.epi_act = g_aff_req.act;
-    a.epi_slope = g_aff_req.slope;
+    a.epi_scale = call.aff->scale;
+    a.epi_shift = call.aff->shift;
+    a.epi_act = call.aff->act;
+    a.epi_slope = call.aff->slope;
   }
+  // fused BatchNorm statistics (es_conv2d_fwd_stats): n [3][Ng] partials, when the caller's buffer holds them
+  auto offer_stats = [&](int n) {
+    const bool ok = mode == MODE_FWD && call.stats_part && n > 0 && (int64_t)n * 3 * a.Ng <= call.stats_floats;
+    a.stats_part = ok ? call.stats_part : nullptr;
+    call.stats_chunks = ok ? n : 0;
+  };
   // caller checked: channels % (128 / EB) == 0, K % (128 / EB) == 0 per step
   int PQ;
   if (mode == MODE_FWD) {
@@ -3055,27 +3058,24 @@ int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
       const int NB = 128 / a.ng, TT = (PQ + NB - 1) / NB;
       const int ntiles = NGI * TT;
       const int nwg = std::min(ntiles, 256);
-      a.stats_part = nullptr;
-      if (mode == MODE_FWD && g_stats_req.part && (int64_t)nwg * 3 * a.Ng <= g_stats_req.floats) {
-        a.stats_part = g_stats_req.part;
-        g_stats_req.chunks = nwg;
-      }
+      offer_stats(nwg);
       // fused BatchNorm-backward reduction over the stored dy (es_conv2d_dgrad_bnred)
-      const BnRedRequest& q = g_bnr_req;
+      const es_norm_t* nm = call.bnr_nm;
+      const es_chain_t* ch = call.bnr_ch;
       bool bnr = false;
-      if (mode == MODE_DGRAD && q.part && (int64_t)nwg * 3 * a.Ng <= q.floats && q.nm && q.ch && q.x &&
-          ((uintptr_t)q.x & 15) == 0 && (q.ch->act == ES_ACT_LRELU || q.ch->act == ES_ACT_RELU) &&
-          (!q.ch->drop.enabled || q.ch->keep) && a.os[3] == a.Ng && a.os[2] == (int64_t)d.W * a.Ng &&
+      if (mode == MODE_DGRAD && call.bnr_part && (int64_t)nwg * 3 * a.Ng <= call.bnr_floats && nm && ch &&
+          call.bnr_x && ((uintptr_t)call.bnr_x & 15) == 0 && (ch->act == ES_ACT_LRELU || ch->act == ES_ACT_RELU) &&
+          (!ch->drop.enabled || ch->keep) && a.os[3] == a.Ng && a.os[2] == (int64_t)d.W * a.Ng &&
           a.os[0] == (int64_t)d.H * d.W * a.Ng) {
-        a.bnr_x = q.x;
-        a.bnr_keep = q.ch->keep;
-        a.bnr_mean = q.nm->mean; a.bnr_invstd = q.nm->invstd; a.bnr_gamma = q.nm->gamma; a.bnr_beta = q.nm->beta;
-        a.bnr_drop = q.ch->drop.enabled != 0;
-        a.bnr_scale = a.bnr_drop ? q.ch->drop.scale : 1.f;
-        a.bnr_dfirst = q.ch->dropout_first;
-        a.bnr_slope = q.ch->act == ES_ACT_LRELU ? q.ch->slope : 0.f;
-        a.bnr_part = q.part;
-        g_bnr_req.chunks = nwg;
+        a.bnr_x = call.bnr_x;
+        a.bnr_keep = ch->keep;
+        a.bnr_mean = nm->mean; a.bnr_invstd = nm->invstd; a.bnr_gamma = nm->gamma; a.bnr_beta = nm->beta;
+        a.bnr_drop = ch->drop.enabled != 0;
+        a.bnr_scale = a.bnr_drop ? ch->drop.scale : 1.f;
+        a.bnr_dfirst = ch->dropout_first;
+        a.bnr_slope = ch->act == ES_ACT_LRELU ? ch->slope : 0.f;
+        a.bnr_part = call.bnr_part;
+        call.bnr_chunks = nwg;
         bnr = true;
       }
       ++g_conv_launches;
@@ -3121,25 +3121,16 @@ int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
     for (int c = 0; c < 4; ++c) a.sp_tpc = std::max(a.sp_tpc, a.sp.tile0[c + 1] - a.sp.tile0[c]);
     row_tiles = NGI * 4 * a.sp_tpc;
   }
-  // fused BatchNorm statistics (es_conv2d_fwd_stats): one [3][Ng] partial per row tile
-  a.stats_part = nullptr;
-  const int chunks = a.sp_merge ? 4 * row_tiles : row_tiles;
-  if (mode == MODE_FWD && g_stats_req.part && a.vec_out && (int64_t)chunks * 3 * a.Ng <= g_stats_req.floats) {
-    a.stats_part = g_stats_req.part;
-    g_stats_req.chunks = chunks;
-  }
+  // one partial per row tile (and class of a merged tile), written by the staged epilogue
+  offer_stats(a.vec_out ? (a.sp_merge ? 4 * row_tiles : row_tiles) : 0);
   if (a.sp_merge) {   // (vec_out: the merged epilogue is the staged one)
     const int NT = 4 * a.Ng / 256;
     if (EB == 2 && g_p256 && (4 * a.Ng) % 256 == 0 && (NT == 1 || NT == 2 || NT == 4) && row_tiles >= 64 && a.out_bf16 &&
         (int64_t)d.N * a.os[0] * 2 < (1ll << 31)) {
-      a.stats_part = nullptr;
-      if (g_stats_req.part && (int64_t)256 * 4 * 3 * a.Ng <= g_stats_req.floats) {
-        a.stats_part = g_stats_req.part;
-        g_stats_req.chunks = 256 * 4;
-      }
+      offer_stats(256 * 4);
       ++g_conv_launches;
       if (aff) {
-        g_aff_req.fused = 1;
+        call.aff_fused = 1;
         if (NT == 1) hipLaunchKernelGGL((conv_p256_kernel<1, true>), dim3(256), dim3(RT), 0, st, a, row_tiles);
         else if (NT == 2) hipLaunchKernelGGL((conv_p256_kernel<2, true>), dim3(256), dim3(RT), 0, st, a, row_tiles);
         else hipLaunchKernelGGL((conv_p256_kernel<4, true>), dim3(256), dim3(RT), 0, st, a, row_tiles);
@@ -3154,43 +3145,43 @@ int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
     if constexpr (SPL == 2) {   // 256 x 128 tiles (a wave's 128 columns within one class) or 256 x 64
       if (a.Ng % 128 == 0) {
         dim3 grid(row_tiles, 4 * a.Ng / 128, 1);
-        launch_ring_grid<MODE_FWD, 256, 128, true, 64, T, 2>(a, grid, st, aff);
+        launch_ring_grid<MODE_FWD, 256, 128, true, 64, T, 2>(a, grid, call, st);
       } else {
         dim3 grid(row_tiles, 4 * a.Ng / 64, 1);
-        launch_ring_grid<MODE_FWD, 256, 64, true, 64, T, 2>(a, grid, st, aff);
+        launch_ring_grid<MODE_FWD, 256, 64, true, 64, T, 2>(a, grid, call, st);
       }
     } else if constexpr (SPL) {   // 256 x 256 tiles of 32-channel steps
       dim3 grid(row_tiles, (4 * a.Ng + 255) / 256, 1);
-      launch_ring_grid<MODE_FWD, 256, 256, true, 64, T, 1>(a, grid, st, aff);
+      launch_ring_grid<MODE_FWD, 256, 256, true, 64, T, 1>(a, grid, call, st);
     } else {
       dim3 grid(row_tiles, (4 * a.Ng + 255) / 256, 1);
-      launch_ring_grid<MODE_FWD, 256, 256, true, 32, T, 0>(a, grid, st, aff);
+      launch_ring_grid<MODE_FWD, 256, 256, true, 32, T, 0>(a, grid, call, st);
     }
     return 1;
   }
 #define ES_RING(MD, BMV, BNV)                                                                  \
-  (sp_weights ? launch_ring<MD, BMV, BNV, true, 64, T, SPL>(a, row_tiles, st, aff)                    \
-              : launch_ring<MD, BMV, BNV, false, 64, T, SPL>(a, row_tiles, st, aff))
+  (sp_weights ? launch_ring<MD, BMV, BNV, true, 64, T, SPL>(a, row_tiles, call, st)                    \
+              : launch_ring<MD, BMV, BNV, false, 64, T, SPL>(a, row_tiles, call, st))
   const bool wide = g_ring256 && big && !shortk && a.Ng >= 256 && a.ng >= 16 && a.vec_out &&
                     (sp_weights || mode == MODE_DGRAD);   // (plain FWD: register spills at 256 x 256)
   if constexpr (SPL == 1) if (wide) {   // split-fp32: 256 x 256 tiles of 32-channel steps
     if (mode == MODE_FWD) {   // (wide FWD is sub-pixel only)
-      launch_ring<MODE_FWD, 256, 256, true, 64, T, 1>(a, row_tiles, st, aff);
+      launch_ring<MODE_FWD, 256, 256, true, 64, T, 1>(a, row_tiles, call, st);
     } else {
-      if (sp_weights) launch_ring<MODE_DGRAD, 256, 256, true, 64, T, 1>(a, row_tiles, st);
-      else launch_ring<MODE_DGRAD, 256, 256, false, 64, T, 1>(a, row_tiles, st);
+      if (sp_weights) launch_ring<MODE_DGRAD, 256, 256, true, 64, T, 1>(a, row_tiles, call, st);
+      else launch_ring<MODE_DGRAD, 256, 256, false, 64, T, 1>(a, row_tiles, call, st);
     }
     return 1;
   }
   if constexpr (SPL == 2) if (wide) {   // pre-split B: 256 x 128 tiles (256 x 256 does not fit the LDS)
-    if (mode == MODE_FWD) launch_ring<MODE_FWD, 256, 128, true, 64, T, 2>(a, row_tiles, st, aff);
-    else if (sp_weights) launch_ring<MODE_DGRAD, 256, 128, true, 64, T, 2>(a, row_tiles, st);
-    else launch_ring<MODE_DGRAD, 256, 128, false, 64, T, 2>(a, row_tiles, st);
+    if (mode == MODE_FWD) launch_ring<MODE_FWD, 256, 128, true, 64, T, 2>(a, row_tiles, call, st);
+    else if (sp_weights) launch_ring<MODE_DGRAD, 256, 128, true, 64, T, 2>(a, row_tiles, call, st);
+    else launch_ring<MODE_DGRAD, 256, 128, false, 64, T, 2>(a, row_tiles, call, st);
     return 1;
   }
   if constexpr (!SPL) if (wide) {
     if (mode == MODE_FWD) {
-      if (sp_weights) launch_ring<MODE_FWD, 256, 256, true, 32, T>(a, row_tiles, st, aff);
+      if (sp_weights) launch_ring<MODE_FWD, 256, 256, true, 32, T>(a, row_tiles, call, st);
       else {   // (not reached: wide FWD is sub-pixel only; launched directly so that no affine variant of
                // this tile, which spills registers, is instantiated)
         dim3 grid(row_tiles, (a.Ng + 255) / 256, 1);
@@ -3198,8 +3189,8 @@ int ring_fd(ConvArgs& a, int mode, hipStream_t st) {
         hipLaunchKernelGGL((conv_ring_kernel<MODE_FWD, 256, 256, false, 32, T>), grid, dim3(RT), 0, st, a);
       }
     } else {
-      if (sp_weights) launch_ring<MODE_DGRAD, 256, 256, true, 32, T>(a, row_tiles, st);
-      else launch_ring<MODE_DGRAD, 256, 256, false, 32, T>(a, row_tiles, st);
+      if (sp_weights) launch_ring<MODE_DGRAD, 256, 256, true, 32, T>(a, row_tiles, call, st);
+      else launch_ring<MODE_DGRAD, 256, 256, false, 32, T>(a, row_tiles, call, st);
     }
     return 1;
   }
@@ -3244,88 +3235,68 @@ int chunk_images(int64_t img_bytes, int N) {
 }  // namespace
 
 namespace {
-// bf16 ring launches over image chunks (es_conv_ring_launch): each chunk on offset base pointers
-// with its first image as the dynamic-rows base; FWD statistics partials appended chunk after
-// chunk; the fused BatchNorm-backward reduction of the persistent DGRAD is not offered to chunked
-// launches (the caller runs the reduction pass).  WGRAD: the chunks' atomic accumulations into dW.
-int ring_launch_chunks(ConvArgs& a, int mode, int nc, hipStream_t st) {
+// Ring launches over chunks of nc images (operands of eb bytes per value; es_conv_ring_launch for
+// bf16, es_conv_ring_launch_f32): each chunk on offset base pointers with its first image as the
+// dynamic-rows base, under a call context of its own.  FWD statistics partials are appended chunk
+// after chunk and the call reports their sum (0 when a chunk wrote none); the fused BatchNorm-backward
+// reduction of the persistent DGRAD is not offered to chunks (the caller runs the reduction pass).
+// bf16 WGRAD: the chunks' atomic accumulations into dW.  The first chunk's "not eligible" is the
+// call's; a later chunk's is an error.
+int ring_launch_chunks(ConvArgs& a, int mode, int nc, int eb, ConvCall& call, hipStream_t st) {
   const es_conv_desc_t& d = a.d;
-  const int N = d.N;
   const int esz = a.out_bf16 ? 2 : 4;
-  const StatsRequest req = g_stats_req;
-  const BnRedRequest bnr = g_bnr_req;
-  g_bnr_req.part = nullptr;
-  int used = 0, rc = 1;
-  bool stats_ok = req.part != nullptr;
-  for (int n0 = 0; n0 < N; n0 += nc) {
+  int used = 0;
+  bool stats_ok = call.stats_part != nullptr;
+  for (int n0 = 0; n0 < d.N; n0 += nc) {
     ConvArgs c = a;
-    c.d.N = std::min(nc, N - n0);
+    c.d.N = std::min(nc, d.N - n0);
     c.nbase = a.nbase + n0;
-    c.a_src = (const char*)a.a_src + (int64_t)n0 * a.as[0] * 2;
+    c.a_src = (const char*)a.a_src + (int64_t)n0 * a.as[0] * eb;
     if (mode == MODE_WGRAD) {
-      c.b_src = (const char*)a.b_src + (int64_t)n0 * a.bs[0] * 2;
+      c.b_src = (const char*)a.b_src + (int64_t)n0 * a.bs[0] * eb;
       c.Kd = c.d.N * d.P * d.Q;
     } else {
       c.out = (char*)a.out + (int64_t)n0 * a.os[0] * esz;
-      c.M = mode == MODE_FWD ? c.d.N * d.P * d.Q : (a.fold ? c.d.N * d.H * d.W : c.d.N * d.Hu * d.Wu);
+      c.M = mode == MODE_FWD ? c.d.N * d.P * d.Q : (int)dgrad_rows(d, c.d.N);
     }
-    if (req.part) g_stats_req = StatsRequest{req.part + (int64_t)used * 3 * a.Ng, req.floats - (int64_t)used * 3 * a.Ng, 0};
-    rc = es_conv_ring_launch(c, mode, st);
+    ConvCall cc;
+    cc.aff = call.aff;
+    if (call.stats_part) {
+      cc.stats_part = call.stats_part + (int64_t)used * 3 * a.Ng;
+      cc.stats_floats = call.stats_floats - (int64_t)used * 3 * a.Ng;
+    }
+    int rc;
+    if (eb == 2) {
+      rc = es_conv_ring_launch(c, mode, cc, st);
+    } else {
+      c.prio = SPL_PRIO;
+      rc = g_f32_split == 2 ? ring_fd<float, 2>(c, mode, cc, st)
+           : g_f32_split ? ring_fd<float, 1>(c, mode, cc, st) : ring_fd<float>(c, mode, cc, st);
+    }
     if (rc <= 0) {
-      if (n0 > 0) {
-        es_set_error("conv bf16 ring: image chunk at %d not eligible", n0);
-        rc = -1;
-      }
-      break;
+      if (n0 == 0) return rc;
+      es_set_error(eb == 2 ? "conv bf16 ring: image chunk at %d not eligible" : "conv f32 ring: chunk %d not eligible",
+                   n0);
+      return -1;
     }
-    if (req.part) {
-      stats_ok = stats_ok && g_stats_req.chunks > 0;
-      used += g_stats_req.chunks;
-    }
+    stats_ok = stats_ok && cc.stats_chunks > 0;
+    used += cc.stats_chunks;
+    call.aff_fused |= cc.aff_fused;
+    call.path |= cc.path;
   }
-  g_stats_req = StatsRequest{req.part, req.floats, rc > 0 && stats_ok ? used : 0};
-  g_bnr_req = bnr;
-  g_bnr_req.chunks = 0;
-  return rc;
+  call.stats_chunks = stats_ok ? used : 0;
+  return 1;
 }
 }  // namespace
 
 // FWD / DGRAD: 1 launched, 0 not eligible (nothing launched), < 0 error
-int es_conv_ring_launch_f32(ConvArgs& a, int mode, hipStream_t st) {
+int es_conv_ring_launch_f32(ConvArgs& a, int mode, ConvCall& call, hipStream_t st) {
   const es_conv_desc_t& d = a.d;
   if (mode == MODE_WGRAD || d.hmap != nullptr || d.stride > 2 || a.splitk) return d.subpixel ? -1 : 0;
-  const int N = d.N;
-  const int ea = 4;   // bytes per value of the gathered operand
-  const int nc = chunk_images(a.as[0] * ea, N);
-  const int esz = a.out_bf16 ? 2 : 4;
-  const StatsRequest req = g_stats_req;
-  int used = 0;
-  bool stats_ok = req.part != nullptr;
-  for (int n0 = 0; n0 < N; n0 += nc) {
-    ConvArgs c = a;
-    c.d.N = std::min(nc, N - n0);
-    c.nbase = a.nbase + n0;
-    c.a_src = (const char*)a.a_src + (int64_t)n0 * a.as[0] * ea;
-    c.out = (char*)a.out + (int64_t)n0 * a.os[0] * esz;
-    c.M = mode == MODE_FWD ? c.d.N * d.P * d.Q : (a.fold ? c.d.N * d.H * d.W : c.d.N * d.Hu * d.Wu);
-    if (req.part) g_stats_req = StatsRequest{req.part + (int64_t)used * 3 * a.Ng, req.floats - (int64_t)used * 3 * a.Ng, 0};
-    c.prio = SPL_PRIO;
-    const int rc = g_f32_split == 2 ? ring_fd<float, 2>(c, mode, st)
-                   : g_f32_split ? ring_fd<float, 1>(c, mode, st) : ring_fd<float>(c, mode, st);
-    if (rc <= 0) {
-      g_stats_req = req;
-      if (n0 == 0) return rc;
-      es_set_error("conv f32 ring: chunk %d not eligible", n0);
-      return -1;
-    }
-    if (req.part) {
-      stats_ok = stats_ok && g_stats_req.chunks > 0;
-      used += g_stats_req.chunks;
-    }
-  }
-  g_stats_req = StatsRequest{req.part, req.floats, stats_ok ? used : 0};
-  g_ring_hit = 1 | (g_f32_split ? 2 : 0) | (d.subpixel ? 4 : 0);
-  return 1;
+  // (one loop for any number of chunks, a single one included)
+  const int rc = ring_launch_chunks(a, mode, chunk_images(a.as[0] * 4, d.N), 4, call, st);
+  if (rc > 0) call.path |= PATH_RING | (g_f32_split ? PATH_SPLIT : 0) | (d.subpixel ? PATH_SUBPIXEL : 0);
+  return rc;
 }
 
 // WGRAD plan of the deterministic fp32 ring kernel: tile, image chunks, K splits per chunk
@@ -3372,14 +3343,16 @@ int64_t es_wgrad_f32_ring_floats(const es_conv_desc_t& d, const int64_t ys[4], c
   return (int64_t)p.nchunks * p.sc * d.K * p.ngt;
 }
 
-// launches the partial kernels and the reduce into dw (torch layout); 1 done, 0 not eligible
+// launches the partial kernels (into call.det_ws) and the reduce into dw (torch layout); 1 done, 0 not
+// eligible
 int es_wgrad_f32_ring(const es_conv_desc_t& d, const void* dy, const int64_t ys[4], const void* x,
-                      const int64_t xs[4], float* dw, float beta, float* ws, int64_t ws_floats, hipStream_t st) {
+                      const int64_t xs[4], float* dw, float beta, ConvCall& call, hipStream_t st) {
   WgF32Plan p;
   if (!wgrad_f32_plan(d, ys, xs, p)) return 0;
+  float* ws = call.det_ws;
   const int64_t need = (int64_t)p.nchunks * p.sc * d.K * p.ngt;
-  if (ws == nullptr || ws_floats < need) {
-    es_set_error("conv wgrad det: workspace of %lld floats, %lld needed", (long long)ws_floats, (long long)need);
+  if (ws == nullptr || call.det_floats < need) {
+    es_set_error("conv wgrad det: workspace of %lld floats, %lld needed", (long long)call.det_floats, (long long)need);
     return -1;
   }
   for (int ch = 0; ch < p.nchunks; ++ch) {
@@ -3442,7 +3415,7 @@ int es_wgrad_f32_ring(const es_conv_desc_t& d, const void* dy, const int64_t ys[
 #undef ES_WF
   }
   launch_wgrad_reduce(ws, p.nchunks * p.sc, d.K, d.C, d.R, d.S, p.ngt, p.spg, dw, beta, st);
-  g_ring_hit = 1 | (g_f32_split ? 2 : 0) | (p.sp ? 4 : 0);
+  call.path |= PATH_RING | (g_f32_split ? PATH_SPLIT : 0) | (p.sp ? PATH_SUBPIXEL : 0);
   return 1;
 }
 

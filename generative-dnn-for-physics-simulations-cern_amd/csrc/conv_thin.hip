@@ -820,7 +820,7 @@ void launch_dgrad(const Thin& t, int rs, int LP, hipStream_t st) {
 }
 
 template <typename T>
-void launch_wgrad(const Thin& t, int rs, int LP, hipStream_t st) {
+void launch_wgrad(const Thin& t, int rs, int LP, ConvCall& call, hipStream_t st) {
   const es_conv_desc_t& d = t.d;
   const int ch = d.C == 1 ? 1 : k1_ch(LP, K1_CH_WG), lp = d.C == 1 ? LP : LP / ch;
   // ~4 blocks per CU, each reducing a strided slice of the pixels
@@ -828,8 +828,8 @@ void launch_wgrad(const Thin& t, int rs, int LP, hipStream_t st) {
   dim3 grid(capped(blocks(t.M, per), THIN_WGRID));
   if (t.det) {   // deterministic mode: one partial slot per block within the caller's workspace
     const int64_t slot = (int64_t)d.K * rs * d.C;
-    grid.x = (unsigned)std::max<int64_t>(1, std::min<int64_t>(grid.x, g_det_req.floats / slot));
-    g_det_req.splits = (int)grid.x;
+    grid.x = (unsigned)std::max<int64_t>(1, std::min<int64_t>(grid.x, call.det_floats / slot));
+    call.det_splits = (int)grid.x;
   }
   if (d.C == 1) {
     if (rs == 4) hipLaunchKernelGGL((c1_wgrad<T, 4>), grid, dim3(NT), 0, st, t);
@@ -857,18 +857,22 @@ void small_dispatch(int K, F&& f) {
 }
 
 // ------------------------------------------------------------------------------- entry points
-// Each returns 1 if it launched (caller checks the launch), 0 if the shape is not a thin conv.
+// Each returns 1 if it launched (caller checks the launch; call.path gets PATH_THIN), 0 if the shape is
+// not a thin conv.
 int es_thin_conv_fwd(const es_conv_desc_t* d, es_dtype_t dt, const void* x, const int64_t xs[4], const void* wk,
-                     const float* bias, void* y, es_dtype_t ydt, const int64_t ys[4], hipStream_t st) {
+                     const float* bias, void* y, es_dtype_t ydt, const int64_t ys[4], ConvCall& call, hipStream_t st) {
   const int rs = d->R * d->S, vn = dt == ES_BF16 ? 8 : 4;
   const bool c1 = c1_ok(d, rs) && ys[1] == 1 && aligned(ys, 8);
   const bool k1 = k1_ok(d, rs, vn) && xs[1] == 1 && xs[3] == d->C && aligned(xs, vn);
-  if (!c1 && !k1 && small_ok(d, dt) && ydt == ES_F32 && xs[1] == 1 && aligned(xs, 4) && ys[1] == 1 &&
-      aligned(ys, 4)) {
-    Thin t{};
-    t.d = *d; t.a = x; t.w = wk; t.bias = bias; t.out = y;
-    for (int i = 0; i < 4; ++i) { t.as[i] = xs[i]; t.os[i] = ys[i]; }
-    t.M = d->N * d->P * d->Q;
+  const bool small = !c1 && !k1 && small_ok(d, dt) && ydt == ES_F32 && xs[1] == 1 && aligned(xs, 4) && ys[1] == 1 &&
+                     aligned(ys, 4);
+  if (!c1 && !k1 && !small) return 0;
+  call.path |= PATH_THIN;
+  Thin t{};
+  t.d = *d; t.a = x; t.w = wk; t.bias = bias; t.out = y;
+  for (int i = 0; i < 4; ++i) { t.as[i] = xs[i]; t.os[i] = ys[i]; }
+  t.M = d->N * d->P * d->Q;
+  if (small) {
     small_dispatch(d->K, [&](auto ko) {
       constexpr int KO = decltype(ko)::value;
       if (d->C == 32)
@@ -878,11 +882,6 @@ int es_thin_conv_fwd(const es_conv_desc_t* d, es_dtype_t dt, const void* x, cons
     });
     return 1;
   }
-  if (!c1 && !k1) return 0;
-  Thin t{};
-  t.d = *d; t.a = x; t.w = wk; t.bias = bias; t.out = y;
-  for (int i = 0; i < 4; ++i) { t.as[i] = xs[i]; t.os[i] = ys[i]; }
-  t.M = d->N * d->P * d->Q;
   const int LP = k1 ? d->C / vn : 1;
   if (dt == ES_BF16) {
     if (ydt == ES_BF16) launch_fwd<bf16, bf16>(t, rs, LP, st); else launch_fwd<bf16, float>(t, rs, LP, st);
@@ -894,33 +893,35 @@ int es_thin_conv_fwd(const es_conv_desc_t* d, es_dtype_t dt, const void* x, cons
 
 int es_thin_conv_dgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, const int64_t ys[4],
                        const void* wd, void* dx, es_dtype_t dxdt, const int64_t dxs[4], float beta,
-                       hipStream_t st) {
+                       ConvCall& call, hipStream_t st) {
   const int rs = d->R * d->S, vn = dt == ES_BF16 ? 8 : 4;
   const bool c1 = c1_ok(d, rs) && ys[1] == 1 && aligned(ys, 8);
   const bool k1 = k1_ok(d, rs, vn) && dxs[1] == 1 && dxs[3] == d->C && aligned(dxs, vn);
   if (!c1 && !k1) return 0;
+  call.path |= PATH_THIN;
   Thin t{};
   t.d = *d; t.a = dy; t.w = wd; t.out = dx; t.beta = beta;
   for (int i = 0; i < 4; ++i) { t.as[i] = ys[i]; t.os[i] = dxs[i]; }
   t.M = d->N * d->H * d->W;
   const int LP = k1 ? d->C / vn : 1;
-  const BnRedRequest& q = g_bnr_req;
+  const es_chain_t* ch = call.bnr_ch;
+  const es_norm_t* nm = call.bnr_nm;
   const int lp8 = d->C / 8;   // the fused kernel's lanes per pixel: 8 channels per lane in both dtypes
-  if (k1 && q.part && q.x && q.nm && q.ch && dt == dxdt && beta == 0.f && (rs == 4 || rs == 9) &&
+  if (k1 && call.bnr_part && call.bnr_x && nm && ch && dt == dxdt && beta == 0.f && (rs == 4 || rs == 9) &&
       pow2(lp8) && lp8 <= 64 && d->C % 8 == 0 &&
       dxs[3] == d->C && dxs[2] == (int64_t)d->W * d->C && dxs[0] == (int64_t)d->H * d->W * d->C &&
-      ((uintptr_t)q.x & 15) == 0 && (q.ch->act == ES_ACT_LRELU || q.ch->act == ES_ACT_RELU) &&
-      (!q.ch->drop.enabled || q.ch->keep)) {
+      ((uintptr_t)call.bnr_x & 15) == 0 && (ch->act == ES_ACT_LRELU || ch->act == ES_ACT_RELU) &&
+      (!ch->drop.enabled || ch->keep)) {
     const dim3 grid(capped(blocks(t.M, NT / lp8), K1_GRID));
-    if ((int64_t)grid.x * 3 * d->C <= q.floats) {
+    if ((int64_t)grid.x * 3 * d->C <= call.bnr_floats) {
       ThinBnr b{};
-      b.x = q.x; b.keep = q.ch->keep;
-      b.mean = q.nm->mean; b.invstd = q.nm->invstd; b.gamma = q.nm->gamma; b.beta = q.nm->beta;
-      b.drop = q.ch->drop.enabled != 0;
-      b.scale = b.drop ? q.ch->drop.scale : 1.f;
-      b.dfirst = q.ch->dropout_first;
-      b.slope = q.ch->act == ES_ACT_LRELU ? q.ch->slope : 0.f;
-      b.part = q.part;
+      b.x = call.bnr_x; b.keep = ch->keep;
+      b.mean = nm->mean; b.invstd = nm->invstd; b.gamma = nm->gamma; b.beta = nm->beta;
+      b.drop = ch->drop.enabled != 0;
+      b.scale = b.drop ? ch->drop.scale : 1.f;
+      b.dfirst = ch->dropout_first;
+      b.slope = ch->act == ES_ACT_LRELU ? ch->slope : 0.f;
+      b.part = call.bnr_part;
       if (dt == ES_BF16) {
         if (rs == 4) hipLaunchKernelGGL((k1_dgrad_bnred<bf16, 4>), grid, dim3(NT), 0, st, t, lp8, b);
         else hipLaunchKernelGGL((k1_dgrad_bnred<bf16, 9>), grid, dim3(NT), 0, st, t, lp8, b);
@@ -928,7 +929,7 @@ int es_thin_conv_dgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, c
         if (rs == 4) hipLaunchKernelGGL((k1_dgrad_bnred<float, 4>), grid, dim3(NT), 0, st, t, lp8, b);
         else hipLaunchKernelGGL((k1_dgrad_bnred<float, 9>), grid, dim3(NT), 0, st, t, lp8, b);
       }
-      g_bnr_req.chunks = (int)grid.x;
+      call.bnr_chunks = (int)grid.x;
       return 1;
     }
   }
@@ -941,18 +942,19 @@ int es_thin_conv_dgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, c
 }
 
 int es_thin_conv_wgrad(const es_conv_desc_t* d, es_dtype_t dt, const void* dy, const int64_t ys[4], const void* x,
-                       const int64_t xs[4], float* dw, hipStream_t st) {
+                       const int64_t xs[4], float* dw, ConvCall& call, hipStream_t st) {
   const int rs = d->R * d->S, vn = dt == ES_BF16 ? 8 : 4;
   const bool c1 = c1_ok(d, rs) && ys[1] == 1 && aligned(ys, 8) && pow2(d->K / 8) && d->K / 8 <= 8;
   const bool k1 = k1_ok(d, rs, vn) && xs[1] == 1 && xs[3] == d->C && aligned(xs, vn);
   if (!c1 && !k1) return 0;
+  call.path |= PATH_THIN;
   Thin t{};
   t.d = *d; t.a = dy; t.b = x; t.out = dw;
   for (int i = 0; i < 4; ++i) { t.as[i] = ys[i]; t.bs[i] = xs[i]; }
   t.M = d->N * d->P * d->Q;
-  t.det = g_det_req.ws != nullptr && (float*)dw == g_det_req.ws;
+  t.det = call.det_ws != nullptr;   // (dw is then the workspace: one partial slot per block)
   const int LP = k1 ? d->C / vn : 1;
-  if (dt == ES_BF16) launch_wgrad<bf16>(t, rs, LP, st);
-  else launch_wgrad<float>(t, rs, LP, st);
+  if (dt == ES_BF16) launch_wgrad<bf16>(t, rs, LP, call, st);
+  else launch_wgrad<float>(t, rs, LP, call, st);
   return 1;
 }

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 from test_f32_ring_gpu import _ref
-from test_kernels_gpu import DEV, _hip, from_act, rel, to_act
+from test_kernels_gpu import DEV, _bnred_operands, _hip, from_act, rel, to_act
 
 pytestmark = pytest.mark.gpu
 
@@ -68,3 +68,87 @@ def test_bf16_ring_image_chunks(case, perf_mode):
     assert rel(part[2], full[2]) < 1e-3
     assert rel(part[0].double(), y) < 2e-2
     assert rel(part[1].double(), gx) < 2e-2
+
+
+# sub-pixel FWD over chunks of 64 + 64 + 2 images: 128 x 128 tiles of 2 pixels x 64 images, 72 per
+# parity class (12 x 12 class pixels), 4 classes -> 288 partials per full chunk; the ragged chunk runs
+# 8-image groups, 16 pixels per tile, 9 tiles per class -> 36
+STATS_CASE = (130, 128, 13, 13, 256, 3, 1, 0, 2)
+STATS_CHUNKS = 288 + 288 + 36
+
+
+@pytest.mark.parametrize("variant", ["bf16", "fp32", "fp32_split"])
+def test_fused_bn_stats_over_image_chunks(variant):
+    """ConvOp.fwd(bn_stats=True) over forced image chunks: every chunk appends its row tiles'
+    BatchNorm partials behind those of the chunks before it, the reported count is their sum, the
+    merged statistics are those of the stored output (expressions and tolerances of
+    test_conv_fused_bn_stats / test_f32_ring_fused_bn_stats) and the output is bitwise the
+    un-chunked one."""
+    hip = _hip()
+    from expertsim import layers
+    from expertsim.layers import ConvOp, NormOp, Upsample
+    N, Cin, H, W, Cout, k, st, pad, up = STATS_CASE
+    dtype = torch.bfloat16 if variant == "bf16" else torch.float32
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(N, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
+    b = torch.randn(Cout, generator=g) + 2.0
+    old_det, old_split = layers.deterministic(), layers.f32_split()
+    layers.set_deterministic(variant != "bf16")
+    layers.set_f32_split(variant == "fp32_split")
+    try:
+        op = ConvOp(torch.nn.Parameter(w.to(DEV)), torch.nn.Parameter(b.to(DEV)), stride=st, pad=pad,
+                    upsample=Upsample((H, W), scale=(up, up)))
+        xa = to_act(x, dtype)
+        full = op.fwd(xa, out_dtype=dtype, bn_stats=True)
+        old = hip.lib().es_conv_set_f32_chunk(64)
+        try:
+            ya = op.fwd(xa, out_dtype=dtype, bn_stats=True)
+        finally:
+            hip.lib().es_conv_set_f32_chunk(old)
+        assert ya.bn_part is not None
+        print("chunks", variant, ya.bn_part[1])
+        assert ya.bn_part[1] == STATS_CHUNKS
+        mk = lambda: NormOp(hip.NORM_BN, torch.ones(Cout, device=DEV), torch.zeros(Cout, device=DEV),
+                            running_mean=torch.zeros(Cout, device=DEV), running_var=torch.ones(Cout, device=DEV))
+        mean, invstd = mk().stats(ya)
+        yt = from_act(ya).double()
+        m_ref = yt.mean(dim=(0, 2, 3))
+        i_ref = 1.0 / torch.sqrt(yt.var(dim=(0, 2, 3), unbiased=False) + 1e-5)
+        print("stats vs fp64", variant, rel(mean.cpu().double(), m_ref), rel(invstd.cpu().double(), i_ref))
+        # (the partials are fp32 arithmetic over the stored values in either precision)
+        assert rel(mean.cpu().double(), m_ref) < 1e-5
+        assert rel(invstd.cpu().double(), i_ref) < 1e-5
+        if variant == "bf16":   # = es_norm_stats over the output of a plain fwd
+            y0 = op.fwd(xa, out_dtype=dtype)
+            assert torch.equal(y0.t, ya.t)
+            n1, n0 = mk(), mk()
+            m1, i1 = n1.stats(ya)
+            m0, i0 = n0.stats(y0)
+            assert rel(m1.cpu(), m0.cpu()) < 1e-5
+            assert rel(i1.cpu(), i0.cpu()) < 1e-5
+            assert rel(n1.rv.cpu(), n0.rv.cpu()) < 1e-5 and rel(n1.rm.cpu(), n0.rm.cpu()) < 1e-5
+        assert torch.equal(ya.t, full.t)
+    finally:
+        layers.set_f32_split(old_split)
+        layers.set_deterministic(old_det)
+
+
+def test_bn_reduce_declined_over_image_chunks(perf_mode):
+    """A chunked DGRAD does not take the fused BatchNorm-backward reduction (its chunks would each
+    write the workgroup slots): dx.bn_sums stays None, the caller runs the reduction pass, and dx is
+    bitwise the plain un-chunked dgrad.  The next, un-chunked call fuses again: a call leaves nothing
+    behind for the one after it."""
+    hip = _hip()
+    op, bn, h, y, stats, ch, gy, kb = _bnred_operands((70, 128, 23, 21, 64, 2), True)   # noqa: F841
+    plain = op.dgrad(gy, y, dx_dtype=torch.bfloat16)
+    old = hip.lib().es_conv_set_f32_chunk(64)
+    try:
+        dx = op.dgrad(gy, y, dx_dtype=torch.bfloat16, bn_reduce=(bn, h, stats, ch))
+    finally:
+        hip.lib().es_conv_set_f32_chunk(old)
+    assert dx.bn_sums is None
+    assert torch.equal(dx.t, plain.t)
+    again = op.dgrad(gy, y, dx_dtype=torch.bfloat16, bn_reduce=(bn, h, stats, ch))
+    assert again.bn_sums is not None
+    assert torch.equal(again.t, plain.t)

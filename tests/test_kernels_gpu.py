@@ -787,16 +787,9 @@ def test_conv_persist_matches_ring(case):
     assert rel(outs[0][2], yr.mean((0, 2, 3)).cpu()) < 1e-2
 
 
-@pytest.mark.parametrize("case", [(64, 128, 46, 46, 64, 2), (37, 128, 23, 21, 64, 2), (33, 64, 9, 7, 128, 2),
-                                  (50, 64, 45, 45, 1, 2), (7, 64, 13, 11, 1, 2), (5, 32, 12, 10, 1, 3)])
-@pytest.mark.parametrize("dfirst", [True, False])
-def test_conv_dgrad_bn_reduce_fused(case, dfirst):
-    """The dgrad fused with the reduction pass of the BatchNorm backward that consumes its output
-    (es_conv2d_dgrad_bnred + es_norm_act_bwd_sums): the persistent DGRAD (generator conv_layers.9 ->
-    conv_layers.6 BatchNorm + Dropout + LeakyReLU) and the thin Cout = 1 dgrad (conv_layers.13 ->
-    conv_layers.10).  The dgrad output is bit-identical to the plain dgrad; the norm backward (dh, dgamma, dbeta, conv-bias sum) equals the unfused two-pass
-    backward up to the summation order of the per-channel sums (fp32: <= 1e-4 relative for the
-    parameter gradients; dh is bf16, within one bf16 rounding)."""
+def _bnred_operands(case, dfirst):
+    """Operands of a dgrad whose output feeds a BatchNorm + Dropout + LeakyReLU backward: the conv,
+    the norm, its input h, y = chain(norm(h)) with the statistics, the chain and the output gradient."""
     hip = _hip()
     from expertsim.layers import Act, ConvOp, NormOp
     N, Cin, H, W, Cout, k = case
@@ -809,11 +802,26 @@ def test_conv_dgrad_bn_reduce_fused(case, dfirst):
     bn = NormOp(hip.NORM_BN, gamma, beta, running_mean=torch.zeros(Cin, device=DEV),
                 running_var=torch.ones(Cin, device=DEV))
     ch = hip.chain_struct(hip.ACT_LRELU, 0.1, hip.dropout_struct(0.2, 4321, 9, enabled=True), dropout_first=dfirst)
-    kb = hip.attach_keep(ch, N * H * W, Cin, DEV)   # noqa: F841 (kept alive for the backward)
+    kb = hip.attach_keep(ch, N * H * W, Cin, DEV)   # (returned: kept alive for the backward)
     y, stats = bn.fwd(h, ch)                     # writes the keep bits the backward reads
     P, Q = H - k + 1, W - k + 1
     gy = Act.nhwc(N, Cout, P, Q, torch.bfloat16, DEV)
     gy.t.copy_(torch.randn(gy.t.shape, generator=torch.Generator().manual_seed(3)).to(DEV))
+    return op, bn, h, y, stats, ch, gy, kb
+
+
+@pytest.mark.parametrize("case", [(64, 128, 46, 46, 64, 2), (37, 128, 23, 21, 64, 2), (33, 64, 9, 7, 128, 2),
+                                  (50, 64, 45, 45, 1, 2), (7, 64, 13, 11, 1, 2), (5, 32, 12, 10, 1, 3)])
+@pytest.mark.parametrize("dfirst", [True, False])
+def test_conv_dgrad_bn_reduce_fused(case, dfirst):
+    """The dgrad fused with the reduction pass of the BatchNorm backward that consumes its output
+    (es_conv2d_dgrad_bnred + es_norm_act_bwd_sums): the persistent DGRAD (generator conv_layers.9 ->
+    conv_layers.6 BatchNorm + Dropout + LeakyReLU) and the thin Cout = 1 dgrad (conv_layers.13 ->
+    conv_layers.10).  The dgrad output is bit-identical to the plain dgrad; the norm backward (dh, dgamma, dbeta, conv-bias sum) equals the unfused two-pass
+    backward up to the summation order of the per-channel sums (fp32: <= 1e-4 relative for the
+    parameter gradients; dh is bf16, within one bf16 rounding)."""
+    Cin = case[1]
+    op, bn, h, y, stats, ch, gy, kb = _bnred_operands(case, dfirst)   # noqa: F841
     outs = []
     for fused in (False, True):
         dx = op.dgrad(gy, y, dx_dtype=torch.bfloat16, bn_reduce=(bn, h, stats, ch) if fused else None)
