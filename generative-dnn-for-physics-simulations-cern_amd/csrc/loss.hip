@@ -265,16 +265,17 @@ __global__ void __launch_bounds__(256) router_colsum_kernel(const float* gates, 
 
 // Router loss terms with gradient into the router (moe.py:258-268,407-434; train/utils.py:372-419,
 // 623-642) and d loss / d logits through the Gumbel softmax (gates = softmax(z / tau)):
-//   ALB  = alb_coef * mean_e exp(1 / (S_e + 1e-6)),      S_e = sum_b gates[b,e]
+//   ALB  = alb_coef * mean_e exp(1 / (S_e + 1e-6)),      S_e = sum_b gates[b,e]   (out[0]: unweighted;
+//          its gradient carries alb_grad = alb_coef * dec_w, the weight of moe.py:424-434)
 //   ENT  = util * sum_e avg_e log(avg_e + 1e-9),          avg_e = S_e / B  (= -entropy * util)
 //   ED   = 0.1 * ed / B * sum_a T[a, idx_a]               (T from router_ed_pairs_kernel, or none)
-// d/dgates[b,e] = alb_coef/E exp(inv_e)(-inv_e^2) + util/B (log(avg_e+1e-9) + avg_e/(avg_e+1e-9))
+// d/dgates[b,e] = alb_grad/E exp(inv_e)(-inv_e^2) + util/B (log(avg_e+1e-9) + avg_e/(avg_e+1e-9))
 //               + 0.2 * ed / B * T[b,e];   dlogits = gates * (dG - <gates, dG>) / tau.
 // out[0] = ALB, out[1] = ENT, out[2] = ED.  T aliases dlogits (each row is read before written).
 __global__ void __launch_bounds__(1024) router_loss_kernel(const float* gates, const int32_t* idx, int B, int E,
-                                                           float tau, float alb_coef, float util, float ed,
-                                                           const float* colsum, float Btot, float* out,
-                                                           float* dlogits) {
+                                                           float tau, float alb_coef, float alb_grad, float util,
+                                                           float ed, const float* colsum, float Btot,
+                                                           float* out, float* dlogits) {
   __shared__ float sh[16];
   __shared__ float gS[64];
   float L = 0.f, ent = 0.f;
@@ -293,7 +294,7 @@ __global__ void __launch_bounds__(1024) router_loss_kernel(const float* gates, c
     const float lg = logf(avg + 1e-9f);
     ent += avg * lg;
     if (threadIdx.x == 0)
-      gS[e] = alb_coef / (float)E * ex * (-inv * inv) + util / Btot * (lg + avg / (avg + 1e-9f));
+      gS[e] = alb_grad / (float)E * ex * (-inv * inv) + util / Btot * (lg + avg / (avg + 1e-9f));
   }
   float edsum = 0.f;
   if (ed != 0.f) {
@@ -333,7 +334,8 @@ __global__ void dp_metrics_merge_kernel(const float* rows, int world, int E, flo
     if (n <= 0.0) continue;
     for (int k = 0; k < 4; ++k) c[k] += n * q[1 + k];
     const double nt = N + n, dl = (double)q[6] - mean;
-    M2 += (n - 1.0) * (double)q[5] * (double)q[5] + dl * dl * N * n / nt;
+    // a rank with one sample carries std_int = NaN (es_gen_losses, like torch.std): its M2 is 0
+    M2 += (n > 1.0 ? (n - 1.0) * (double)q[5] * (double)q[5] : 0.0) + dl * dl * N * n / nt;
     mean += dl * n / nt;
     N = nt;
   }
@@ -406,7 +408,7 @@ __global__ void step_metrics_kernel(const float* mbuf, int E, const float* rl, c
         for (int b = a + 1; b < E; ++b) dli += fabsf(mbuf[a * 9 + 6] - mbuf[b * 9 + 6]);
       diff = -(dli * diff_strength) * diff_strength;
     }
-    alb = alb_on ? rl[0] / dec_w : 0.f;
+    alb = alb_on ? rl[0] : 0.f;
     ent = util_on ? rl[1] : 0.f;
     ed = ed_on ? rl[2] : 0.f;
     rloss = trained ? ed + gan + diff + ent + dec_w * alb : 0.f;   // moe.py:424-442
@@ -489,9 +491,9 @@ extern "C" int es_router_alb(const float* gates, int B, int E, float tau, float 
 }
 
 extern "C" int es_router_loss(const float* gates, const int32_t* idx, const float* feat, int B, int E, float tau,
-                              float alb_coef, float util_strength, float ed_strength, const float* colsum,
-                              int B_total, const float* feat_all, const int32_t* idx_all, int B_all, float* out,
-                              float* dlogits, es_stream_t stream) {
+                              double alb_coef, double dec_w, float util_strength, float ed_strength,
+                              const float* colsum, int B_total, const float* feat_all, const int32_t* idx_all,
+                              int B_all, float* out, float* dlogits, es_stream_t stream) {
   ES_CHECK_ARG(B > 0 && E >= 1 && E <= 64, "router_loss: B=%d E=%d (E <= 64)", B, E);
   ES_CHECK_ARG(ed_strength == 0.f || (feat && idx), "router_loss: ED needs feat and idx");
   hipStream_t st = (hipStream_t)stream;
@@ -500,8 +502,9 @@ extern "C" int es_router_loss(const float* gates, const int32_t* idx, const floa
   if (ed_strength != 0.f)
     hipLaunchKernelGGL(router_ed_pairs_kernel, dim3((B + 255) / 256, E), dim3(256), 0, st, feat, B, feat_all,
                        idx_all, B_all, E, dlogits);
-  hipLaunchKernelGGL(router_loss_kernel, dim3(1), dim3(1024), 0, st, gates, idx, B, E, tau, alb_coef, util_strength,
-                     ed_strength, colsum, (float)B_total, out, dlogits);
+  // the gradient's coefficient is the double product rounded once (what the caller used to pass)
+  hipLaunchKernelGGL(router_loss_kernel, dim3(1), dim3(1024), 0, st, gates, idx, B, E, tau, (float)alb_coef,
+                     (float)(alb_coef * dec_w), util_strength, ed_strength, colsum, (float)B_total, out, dlogits);
   ES_CHECK_LAUNCH();
   return ES_OK;
 }

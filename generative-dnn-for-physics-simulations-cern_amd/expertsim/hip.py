@@ -172,8 +172,8 @@ _SIGS = {
     "es_image_expsum_bwd": (C.c_int, [P, C.c_int, P, P, P, P, C.c_float, P]),
     "es_router_gumbel": (C.c_int, [P, P, C.c_int, C.c_int, C.c_float, P, P, P, P]),
     "es_router_alb": (C.c_int, [P, C.c_int, C.c_int, C.c_float, C.c_float, P, P, P]),
-    "es_router_loss": (C.c_int, [P, P, P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, P,
-                                 C.c_int, P, P, C.c_int, P, P, P]),
+    "es_router_loss": (C.c_int, [P, P, P, C.c_int, C.c_int, C.c_float, C.c_double, C.c_double, C.c_float,
+                                 C.c_float, P, C.c_int, P, P, C.c_int, P, P, P]),
     "es_router_colsum": (C.c_int, [P, C.c_int, C.c_int, P, P]),
     "es_router_dispatch": (C.c_int, [P, C.c_int, C.c_int, P, P, P]),
     "es_dp_metrics_merge": (C.c_int, [P, C.c_int, C.c_int, P, P]),

@@ -357,7 +357,7 @@ class MoEWrapper(nn.Module):
                     feat_all, idx_all, B_all = ddp.all_gather(self._ed_feat), ddp.all_gather(idx), B_tot
             hip.call("es_router_loss", hip.ptr(gates), hip.ptr(idx) if ed_on else None,
                      hip.ptr(self._ed_feat) if ed_on else None, B, E, float(tau),
-                     float(rc.alb_strength * dec_w), float(rc.util_strength), float(rc.ed_strength),
+                     float(rc.alb_strength), float(dec_w), float(rc.util_strength), float(rc.ed_strength),
                      hip.ptr(colsum), B_tot, hip.ptr(feat_all), hip.ptr(idx_all), B_all,
                      hip.ptr(rl), hip.ptr(dlogits), hip.stream_ptr())
             if ddp is not None and ed_on:

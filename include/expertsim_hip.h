@@ -569,7 +569,9 @@ int es_router_alb(const float* gates, int B, int E, float tau, float coef, float
                   float* dlogits, es_stream_t stream);
 /* All router-loss terms that carry gradient (moe.py:258-268,407-434; train/utils.py:372-395
  * calculate_expert_distribution_loss, 398-419 calculate_expert_utilization_entropy, 623-642 ALB):
- * out[0] = alb_coef*mean_e exp(1/(S_e+1e-6)); out[1] = util*sum_e avg_e*log(avg_e+1e-9)
+ * out[0] = alb_coef*mean_e exp(1/(S_e+1e-6)), the unweighted value the metric dict reports; its
+ * gradient is weighted by dec_w (moe.py:424-434: the coefficient is (float)(alb_coef*dec_w), so
+ * dec_w = 0 gives a finite out[0] and no ALB gradient); out[1] = util*sum_e avg_e*log(avg_e+1e-9)
  * (= -entropy*util, avg = S/B_total); out[2] = 0.1*ed/B_total*sum_{a,b: idx_a=idx_b} |feat_a - feat_b|
  * (cdist of the [B,1] per-sample photon sums, gated by the straight-through one-hot gates);
  * dlogits = d(sum of the three)/d logits through the Gumbel softmax, for the B rows of `gates`.
@@ -577,9 +579,9 @@ int es_router_alb(const float* gates, int B, int E, float tau, float coef, float
  * (<= 0: B), feat_all / idx_all [B_all] = the all-gathered ED features (NULL: this call's rows); out
  * then holds this rank's share of the ED sum.  feat / idx may be NULL when ed_strength == 0. */
 int es_router_loss(const float* gates, const int32_t* idx, const float* feat, int B, int E, float tau,
-                   float alb_coef, float util_strength, float ed_strength, const float* colsum, int B_total,
-                   const float* feat_all, const int32_t* idx_all, int B_all, float* out, float* dlogits,
-                   es_stream_t stream);
+                   double alb_coef, double dec_w, float util_strength, float ed_strength, const float* colsum,
+                   int B_total, const float* feat_all, const int32_t* idx_all, int B_all, float* out,
+                   float* dlogits, es_stream_t stream);
 /* Device-side expert dispatch (moe.py:121-123 `(idx == i).nonzero()` per expert, without the host
  * round trip): perm[B] = the batch rows grouped by expert, each group in batch order;
  * offs[E+1] = start of each group (offs[E] = B). */
@@ -589,7 +591,8 @@ int es_router_colsum(const float* gates, int B, int E, float* out, es_stream_t s
 /* The train step's metric dict (moe.py:480-502) in one launch: out[11 + 8E] = gen, disc, div,
  * intensity, aux (means over the experts of mbuf [E][9] = per expert total, gen, div, int, aux,
  * std_int, mean_int, w, disc), router, ED, differentiation, entropy, ALB, gan (moe.py:255-434 from
- * rl = [ALB*dec_w, entropy, ED]), then per expert gen_i, disc_i, div_i, int_i, aux_i, std_int_i,
+ * rl = es_router_loss's out = [ALB, entropy, ED]; router = ED + gan + differentiation + entropy +
+ * dec_w*ALB), then per expert gen_i, disc_i, div_i, int_i, aux_i, std_int_i,
  * mean_int_i, n_i (counts int32 or countsf float).  flags: 1 router (E > 1), 2 router trained this
  * epoch, 4 ALB on, 8 entropy on, 16 ED on. */
 int es_step_metrics(const float* mbuf, int E, const float* rl, const int32_t* counts, const float* countsf,

@@ -350,8 +350,7 @@ def router_forward(P, cond, tau, gumbel_exp):
         if i < 3:
             x = F.leaky_relu(x, SLOPE)
     logits = x
-    g = -gumbel_exp.log()
-    return ((logits + g) / tau).softmax(-1), logits
+    return gumbel_gates(logits, gumbel_exp, tau), logits
 
 
 def sdi_gan_regularization(l1, l2, n1, n2, std, di):
@@ -363,9 +362,45 @@ def sdi_gan_regularization(l1, l2, n1, n2, std, di):
     return torch.mean(std) * torch.mean(dl) * di
 
 
+def gumbel_gates(logits, gumbel_exp, tau):
+    """torch F.gumbel_softmax(hard=False) with injected Exp(1) draws (routers/router.py:23)."""
+    g = -gumbel_exp.log()
+    return ((logits + g) / tau).softmax(-1)
+
+
+def router_loss_terms(gates_soft, gates, mean_in_batch, rc):
+    """The router-loss terms that carry gradient into the router: utilisation entropy
+    (train/utils.py:398-419, moe.py:258-262), expert distribution (train/utils.py:372-395,
+    moe.py:264-268) and adaptive load balancing (train/utils.py:623-642, moe.py:407), each 0 when its
+    strength is 0.  Returns (ent, ed, alb); alb is unweighted (moe.py:424-434 applies dec_w)."""
+    if rc["util_strength"] != 0:
+        avg = gates_soft.mean(0)
+        ent = -(-torch.sum(avg * torch.log(avg + 1e-9), dim=-1) * rc["util_strength"])
+    else:
+        ent = torch.tensor(0.0)
+    if rc["ed_strength"] != 0:
+        dist = torch.cdist(mean_in_batch, mean_in_batch, p=2)
+        sim = gates @ gates.T
+        ed = 0.1 * (torch.sum(sim * dist) / sim.size(0)) * rc["ed_strength"]
+    else:
+        ed = torch.tensor(0.0)
+    alb = (torch.exp(1.0 / (gates_soft.sum(0) + 1e-6)).mean() * rc["alb_strength"]
+           if rc["alb_strength"] != 0 else torch.tensor(0.0))
+    return ent, ed, alb
+
+
 def intensity_regularization(img, intensity, strength):
     """moe.py:590-642."""
-    s = torch.sum(torch.exp(img) - 1, dim=[2, 3])
+    return intensity_terms(photon_sums(img), intensity, strength)
+
+
+def photon_sums(img):
+    """moe.py:611-616: per-image (and channel) sum of exp(x) - 1, [B, C]."""
+    return torch.sum(torch.exp(img) - 1, dim=[2, 3])
+
+
+def intensity_terms(s, intensity, strength):
+    """moe.py:618-642 from the photon sums s [B, 1]: (L1 term, s, std, mean)."""
     return F.l1_loss(s, intensity.view(-1, 1)) * strength, s, s.std(), s.mean()
 
 
@@ -518,25 +553,13 @@ class OracleMoE:
         rc = c
         if E > 1:                                                     # moe.py:213-442
             gan = torch.stack(gen_losses).mean() * rc["gan_strength"]
-            if rc["util_strength"] != 0:
-                avg = gates_soft.mean(0)
-                ent = -(-torch.sum(avg * torch.log(avg + 1e-9), dim=-1) * rc["util_strength"])
-            else:
-                ent = torch.tensor(0.0)
-            if rc["ed_strength"] != 0:
-                dist = torch.cdist(mean_in_batch, mean_in_batch, p=2)
-                sim = gates @ gates.T
-                ed = 0.1 * (torch.sum(sim * dist) / sim.size(0)) * rc["ed_strength"]
-            else:
-                ed = torch.tensor(0.0)
+            ent, ed, alb = router_loss_terms(gates_soft, gates, mean_in_batch, rc)
             if rc["diff_strength"] != 0:
                 dli = sum(F.l1_loss(mean_int[a].unsqueeze(0), mean_int[b].unsqueeze(0))
                           for a, b in combinations(range(E), 2)) * rc["diff_strength"]
             else:
                 dli = torch.tensor(0.0)
             diff = -dli * rc["diff_strength"]
-            alb = (torch.exp(1.0 / (gates_soft.sum(0) + 1e-6)).mean() * rc["alb_strength"]
-                   if rc["alb_strength"] != 0 else torch.tensor(0.0))
             alpha = min(max(epoch / rc["alpha"], 0.0), 1.0)
             dec_w = rc["min_weight"] + (1.0 - rc["min_weight"]) * alpha
             router_loss = ed + gan + diff + ent + dec_w * alb
