@@ -199,7 +199,16 @@ _SIGS = {
     "es_bn_fold_batch": (C.c_int, [C.c_int, P, P, P, P, P, P, P, P, P]),
     "es_sim_finish": (C.c_int, [P, P, P, P, P, C.c_int, P, P, P]),
     "es_dropout_mask": (C.c_int, [P, I64, P, P]),
+    "es_wasserstein_1d_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "es_wasserstein_1d": (C.c_int, [P, I64, C.c_int, P, P, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    P, P, C.c_size_t, P]),
+    "es_wasserstein_lds_max": (C.c_int, []),
 }
+
+# the largest nu + nv es_wasserstein_1d sorts in LDS (ES_WS_LDS_MAX of include/expertsim_hip.h; lib()
+# checks it against the built library); larger problems take the global-memory passes
+WS_LDS_MAX = 8192
+WS_MAX = 1 << 20
 
 
 class HipError(RuntimeError):
@@ -229,6 +238,9 @@ def lib():
             if L.es_struct_size(i) != C.sizeof(st):
                 raise HipError(f"{st.__name__}: ctypes size {C.sizeof(st)} != C size {L.es_struct_size(i)} "
                                f"(bindings out of date with include/expertsim_hip.h)")
+        if L.es_wasserstein_lds_max() != WS_LDS_MAX:
+            raise HipError(f"WS_LDS_MAX {WS_LDS_MAX} != the library's {L.es_wasserstein_lds_max()} "
+                           f"(bindings out of date with include/expertsim_hip.h)")
         _lib = L
     return _lib
 

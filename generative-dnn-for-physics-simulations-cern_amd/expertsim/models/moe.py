@@ -33,6 +33,7 @@ from __future__ import annotations
 import contextlib
 import copy
 import ctypes as C
+import gc
 
 import numpy as np
 import torch
@@ -630,6 +631,56 @@ class MoEWrapper(nn.Module):
                "ws_std": ws_std, **{f"ws_std_{i}": ws_std_exp[i] for i in range(self.n_experts)}, "epoch": epoch}
         return log
 
+    @torch.no_grad()
+    def evaluate_device(self, epoch, y_test, x_test, cfg, *, seed=0, sample_offset=0, routing="sample",
+                        fused=True, graph=True, details=False):
+        """The metrics of evaluate (same keys) from the simulate path, without a host round trip until
+        the result: real sums by es_channel_sums, repetition j of the n_calc = min(epoch // 5 + 1, 5) by
+        simulate(sums=True) -- j = 0 with simulate's own noise draw, j > 0 with es_randn_dev(seed + j) on
+        SIM_NOISE_STREAM at the same element offsets -- then the (E + 1) x 5 Wasserstein distances per
+        repetition on the device (train.utils.ws_across_experts_device) and ONE device-to-host copy of
+        the [R, E + 1, 5] result, closed by train.utils.ws_summary.
+
+        The Gumbel draws depend on (seed, sample_offset + i) only, so every repetition routes
+        identically (the reference routes once per evaluate call), and the metrics are a function of
+        (parameters, inputs, seed, sample_offset): bitwise equal on rerun, whatever torch's global RNG.
+        details=True adds the device tensors sums_real [N, 5], sums_gen [R, N, 5], expert [N], ws
+        [R, E + 1, 5].  Like simulate, reads training state and changes none; HIP device only."""
+        from ..train.utils import channel_sums, ws_across_experts_device, ws_summary
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise hip.HipError("MoEWrapper.evaluate_device runs on the HIP device only (no CPU fallback)")
+        shape = tuple(cfg.dataset.input_image_shape)
+        x = x_test if isinstance(x_test, torch.Tensor) else torch.as_tensor(np.asarray(x_test))
+        x = x.reshape(-1, *shape)
+        E, nd, N = self.n_experts, self.noise_dim, int(x.shape[0])
+        with torch.cuda.device(dev):
+            sums_real = channel_sums(x.to(dev, dtype=torch.float32), log_domain=True)
+            cond = torch.as_tensor(y_test).to(device=dev, dtype=torch.float32).contiguous()
+            if cond.shape[0] != N:
+                raise ValueError(f"evaluate_device: {cond.shape[0]} conditions for {N} images")
+            R = min(epoch // 5 + 1, 5)
+            sums_gen = torch.empty(R, N, 5, dtype=torch.float64, device=dev)
+            expert = None
+            for j in range(R):
+                noise = None
+                if j > 0:
+                    noise = torch.empty(N, nd, dtype=torch.float32, device=dev)
+                    hip.call("es_randn_dev", hip.ptr(noise), N * nd, (int(seed) + j) & 0xFFFFFFFFFFFFFFFF,
+                             self.SIM_NOISE_STREAM, None, 0, int(sample_offset) * nd, hip.stream_ptr())
+                sim = self.simulate(cond, seed=seed, sample_offset=sample_offset, noise=noise, routing=routing,
+                                    sums=True, fused=fused, graph=graph)
+                sums_gen[j].copy_(sim["sums"])
+                if expert is None:
+                    expert = sim["expert"]
+            ws = ws_across_experts_device(sums_real, sums_gen, expert, E)
+            ws_mean, ws_std, ws_mean_exp, ws_std_exp = ws_summary(ws.cpu().numpy())   # the one D2H copy
+        log = {"ws_mean": ws_mean, **{f"ws_mean_{i}": ws_mean_exp[i] for i in range(E)},
+               "ws_std": ws_std, **{f"ws_std_{i}": ws_std_exp[i] for i in range(E)}, "epoch": epoch}
+        if details:
+            log.update(sums_real=sums_real, sums_gen=sums_gen, expert=expert, ws=ws)
+        return log
+
     # ---------------------------------------------------------------------------- simulation
     # Philox stream ids of the simulation draws (DeviceRNG's step streams start at 1 << 24)
     SIM_NOISE_STREAM = 0x51D00001
@@ -825,6 +876,7 @@ class ExpertGraphs:
         self.replays = 0
         self._used = []
         self._ready = None
+        self._collected = False
 
     def clear(self):
         self.graphs = {}
@@ -834,6 +886,7 @@ class ExpertGraphs:
         self._ready = torch.cuda.Event()
         self._ready.record()
         self._used = []
+        self._collected = False
 
     def run(self, key, fn):
         from ..layers import count_batches, nbt_added, nbt_snapshot
@@ -857,9 +910,18 @@ class ExpertGraphs:
             # equal to the eager steps with this device synchronisation, which torch.cuda.graph's
             # own capture protocol also performs).  A capture happens once per (expert, B_e) key.
             torch.cuda.synchronize()
+            if not self._collected:
+                # Once per step that captures (torch.cuda.graph does both per capture, ~10 ms each): a
+                # dropped MoEWrapper sits in reference cycles and keeps its graphs' private memory pools
+                # until the cyclic collector happens to run, and an allocation that fails inside a
+                # capture cannot fall back on the allocator's cached blocks.  Models built one after
+                # another in one process (tests/test_configs_gpu.py: E = 8 neutron56 after 35 other
+                # tests) otherwise run out of device memory here, or not, by the collector's timing.
+                gc.collect()
+                torch.cuda.empty_cache()
+                self._collected = True
             g = torch.cuda.CUDAGraph()
-            # capture on the expert's own stream (torch.cuda.graph's gc.collect + empty_cache per
-            # capture cost ~10 ms; the experts' captures do not need them)
+            # capture on the expert's own stream
             with torch.cuda.stream(st):
                 g.capture_begin(pool=self.pools[e])
                 try:

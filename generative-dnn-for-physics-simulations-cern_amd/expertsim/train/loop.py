@@ -5,7 +5,8 @@ step is ``MoEWrapper.train_step`` on the HIP path.  Metrics are fetched to the h
 (the reference does ``.cpu().item()`` per key, loop.py:136-148).  With WORLD_SIZE > 1 (torchrun),
 every rank trains on its own shard and gradients are all-reduced over RCCL (expertsim/train/ddp.py).
 ``evaluate_epoch`` (loop.py:185-256) produces the Wasserstein metrics of MoEWrapper.evaluate on the
-HIP path.  Checkpoints (hooks.CheckpointSaver, training_utils) and the
+HIP path, or with ``train.eval_on_device`` those of
+MoEWrapper.evaluate_device (everything up to the distances on the device).  Checkpoints (hooks.CheckpointSaver, training_utils) and the
 EMAHelper (ema.py) follow loop.py:36-107,357-418; resume restores weights, optimizer moments and
 the step counters.  Plotting and W&B stay out of scope.
 """
@@ -96,16 +97,26 @@ def train_epoch(moe, train_loader, gen_optims, disc_optims, aux_reg_optims, rout
 
 @torch.no_grad()
 def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) -> Dict:
-    """Reference loop.py:185-256 without the plots: per-batch MoEWrapper.evaluate, averaged."""
+    """Reference loop.py:185-256 without the plots: per-batch MoEWrapper.evaluate, averaged.
+    train.eval_on_device: MoEWrapper.evaluate_device instead (routing, generation and the Wasserstein
+    distances on the device, seeded by train.rng_seed; a sample's draws depend on its position in the
+    test set, not on the loader's batch size)."""
     moe.eval()
     keys = ["ws_mean", *[f"ws_mean_{i}" for i in range(moe.n_experts)],
             "ws_std", *[f"ws_std_{i}" for i in range(moe.n_experts)]]
     acc: Dict[str, List[float]] = {k: [] for k in keys}
+    on_device = bool(cfg.train.get("eval_on_device", False))
+    seen = 0                                   # test samples in earlier batches
     for b, batch in enumerate(test_loader):
         if max_batches is not None and b >= max_batches:
             break
         real_images, _, cond, std, intensity, true_positions = batch
-        m = moe.evaluate(epoch, cond.to(device), real_images, true_positions, std, intensity, cfg, device)
+        if on_device:
+            m = moe.evaluate_device(epoch, cond.to(device), real_images, cfg,
+                                    seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=seen)
+            seen += int(cond.shape[0])
+        else:
+            m = moe.evaluate(epoch, cond.to(device), real_images, true_positions, std, intensity, cfg, device)
         for k in keys:
             acc[k].append(float(m[k]))
     return {k: (sum(v) / len(v) if v else 0.0) for k, v in acc.items()}

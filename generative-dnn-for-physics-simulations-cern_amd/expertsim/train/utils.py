@@ -15,6 +15,12 @@ sums in one pass, in fp64.  Only the [N,5] sums cross to the host, where the 1-D
 distances are taken with scipy.stats.wasserstein_distance exactly as the reference does (a host
 O(N log N) sort over a few thousand values per channel).  There is no CPU fallback for the sums:
 ``channel_sums`` raises when the HIP library or device is missing.
+
+Device evaluation (MoEWrapper.evaluate_device, opt-in): ``wasserstein_1d_device`` /
+``ws_across_experts_device`` take the same distances on the device (es_wasserstein_1d,
+csrc/wasserstein.hip: scipy's arithmetic term for term) from the batch-ordered sums and the expert
+vector; only the [n_calc, E + 1, 5] distances cross to the host, where ``ws_summary`` closes them as
+calculate_joint_ws_across_experts does.
 """
 from __future__ import annotations
 
@@ -195,6 +201,113 @@ def get_predictions_from_experts_results(num_samples, noise_dim, device, y_test,
             hip.call("es_sim_finish", C.byref(v), h6.ptr, hip.ptr(live), hip.ptr(perm), hip.ptr(offs[e:e + 1]), 1,
                      hip.ptr(dst), None, hip.stream_ptr())
     return out.double().cpu().numpy().reshape(num_samples, *shape_images)
+
+
+# ------------------------------------------------------------------------------ device Wasserstein
+_WS_WORK = {}      # device -> workspace of es_wasserstein_1d's global-memory path (grown, never shrunk)
+_WS_SEG = {}       # (device, rows) -> the default one-segment bounds [[0, rows]]
+
+
+def _ws_workspace(nbytes: int, device) -> torch.Tensor:
+    w = _WS_WORK.get(device)
+    if w is None or w.numel() < nbytes:
+        w = _WS_WORK[device] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+    return w
+
+
+def _ws_side(name, t, seg, idx, cap):
+    hip.require_device(t)
+    if t.dim() != 2 or t.dtype != torch.float64 or t.shape[0] == 0 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"wasserstein_1d_device: {name} must be a non-empty fp64 [rows, C] tensor with unit "
+                         f"column stride, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    rows = int(t.shape[0])
+    if seg is None:
+        key = (t.device, rows)
+        seg = _WS_SEG.get(key)
+        if seg is None:
+            seg = _WS_SEG[key] = torch.tensor([[0, rows]], dtype=torch.int32, device=t.device)
+    if seg.dtype != torch.int32 or seg.device != t.device or seg.numel() % 2 or not seg.is_contiguous():
+        raise ValueError(f"wasserstein_1d_device: {name}_seg must be a contiguous device int32 [n_seg, 2] tensor")
+    if idx is not None and (idx.dtype != torch.int32 or idx.device != t.device or not idx.is_contiguous()
+                            or idx.numel() != rows):
+        raise ValueError(f"wasserstein_1d_device: {name}_idx must be a contiguous device int32 [{rows}] tensor")
+    return rows, seg, idx, rows if cap is None else int(cap)
+
+
+def wasserstein_1d_device(u, v, u_seg=None, v_seg=None, u_idx=None, v_idx=None, u_cap=None,
+                          v_cap=None) -> torch.Tensor:
+    """[n_seg, C] fp64 device tensor of 1-D Wasserstein-1 distances (HIP kernel es_wasserstein_1d,
+    scipy.stats.wasserstein_distance term for term): entry (s, c) compares column c of the u rows of
+    segment s with column c of the v rows of segment s.
+
+    u [rows_u, C], v [rows_v, C]: device fp64, any row stride.  u_seg / v_seg: device int32 [n_seg, 2]
+    bounds (default: one segment over all rows) of positions in u_idx / v_idx (device int32 [rows],
+    default: the rows themselves).  u_cap / v_cap: host upper bounds of a segment's length (default: the
+    rows).  Everything is read on the device: no host synchronisation; the workspace of problems past
+    hip.WS_LDS_MAX values is cached per device (one buffer: such calls on different streams of a device
+    must not overlap)."""
+    ur, u_seg, u_idx, u_cap = _ws_side("u", u, u_seg, u_idx, u_cap)
+    vr, v_seg, v_idx, v_cap = _ws_side("v", v, v_seg, v_idx, v_cap)
+    ch = int(u.shape[1])
+    n_seg = u_seg.numel() // 2
+    if v.device != u.device or int(v.shape[1]) != ch or v_seg.numel() // 2 != n_seg:
+        raise ValueError(f"wasserstein_1d_device: u {tuple(u.shape)} with {n_seg} segments against "
+                         f"v {tuple(v.shape)} with {v_seg.numel() // 2}")
+    out = torch.empty(n_seg, ch, dtype=torch.float64, device=u.device)
+    with torch.cuda.device(u.device):
+        need = int(hip.lib().es_wasserstein_1d_workspace(n_seg, ch, u_cap, v_cap))
+        work = _ws_workspace(need, u.device) if need else None
+        hip.call("es_wasserstein_1d", hip.ptr(u), u.stride(0), ur, hip.ptr(u_idx), hip.ptr(u_seg),
+                 hip.ptr(v), v.stride(0), vr, hip.ptr(v_idx), hip.ptr(v_seg), n_seg, ch, u_cap, v_cap,
+                 hip.ptr(out), hip.ptr(work), need, hip.stream_ptr())
+    return out
+
+
+def ws_across_experts_device(ch_org, ch_gen, expert, n_experts) -> torch.Tensor:
+    """The distances of calculate_joint_ws_across_experts on the device: ch_org [N, 5] (real sums) and
+    ch_gen [R, N, 5] (R repetitions of generated sums) fp64, both in batch order, expert [N] int32.
+    Returns [R, E + 1, 5]: row 0 the joint distance, row 1 + e expert e's (0 for an expert without
+    rows).  One es_router_dispatch gives perm / offs; the segments are (0, N) and (offs[e], offs[e + 1])
+    with perm as the row index on both sides (no gather copy), and the R repetitions are rows r * N ..
+    of one [R * N, 5] v side, so all R * (E + 1) * 5 problems go out in one es_wasserstein_1d call."""
+    hip.require_device(ch_org)
+    dev, E = ch_org.device, int(n_experts)
+    N, R = int(ch_org.shape[0]), int(ch_gen.shape[0])
+    if ch_org.dim() != 2 or tuple(ch_gen.shape) != (R, N, ch_org.shape[1]) or tuple(expert.shape) != (N,):
+        raise ValueError(f"ws_across_experts_device: ch_org {tuple(ch_org.shape)}, ch_gen {tuple(ch_gen.shape)}, "
+                         f"expert {tuple(expert.shape)}")
+    if R * N > np.iinfo(np.int32).max:
+        raise ValueError(f"ws_across_experts_device: {R} x {N} rows exceed int32")
+    expert = expert.to(device=dev, dtype=torch.int32).contiguous()
+    perm = torch.empty(N, dtype=torch.int32, device=dev)
+    offs = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        hip.call("es_router_dispatch", hip.ptr(expert), N, E, hip.ptr(perm), hip.ptr(offs), hip.stream_ptr())
+    seg = torch.empty(E + 1, 2, dtype=torch.int32, device=dev)
+    seg[0, 0] = 0
+    seg[0, 1] = N
+    seg[1:, 0] = offs[:-1]
+    seg[1:, 1] = offs[1:]
+    shift = torch.arange(R, dtype=torch.int32, device=dev) * N
+    u_seg = seg.repeat(R, 1)
+    v_seg = (seg[None] + shift[:, None, None]).reshape(R * (E + 1), 2).contiguous()
+    v_idx = (perm[None] + shift[:, None]).reshape(R * N).contiguous()
+    gen = ch_gen.to(torch.float64).contiguous().view(R * N, -1)
+    ws = wasserstein_1d_device(ch_org.to(torch.float64), gen, u_seg, v_seg, perm, v_idx, u_cap=N, v_cap=N)
+    return ws.view(R, E + 1, -1)
+
+
+def ws_summary(ws):
+    """Closing arithmetic of calculate_joint_ws_across_experts (train/utils.py:117-176) on the host copy
+    of ws_across_experts_device's [R, E + 1, 5] result (a pure numpy function): channel means per
+    repetition, then mean / std over the repetitions.  Returns (ws_mean, ws_std, ws_mean_exp [E],
+    ws_std_exp [E])."""
+    ws = np.asarray(ws, dtype=np.float64)
+    if ws.ndim != 3 or ws.shape[1] < 2:
+        raise ValueError(f"ws_summary: expected [R, E + 1, C], got {ws.shape}")
+    ws_runs = ws[:, 0].mean(axis=1)
+    ws_exp_runs = ws[:, 1:].mean(axis=2)
+    return ws_runs.mean(), ws_runs.std(), ws_exp_runs.mean(axis=0), ws_exp_runs.std(axis=0)
 
 
 def calculate_joint_ws_across_experts(n_calc, x_tests: List, y_tests: List, generators: List, ch_org,

@@ -18,6 +18,7 @@
 #ifndef EXPERTSIM_HIP_H
 #define EXPERTSIM_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -681,6 +682,28 @@ int es_dropout_mask(uint8_t* out, int64_t n, const es_dropout_t* d, es_stream_t 
  * computes it; log_domain != 0 applies expm1 first (moe.py:646, train/utils.py:198). */
 int es_channel_sums(const es_view_t* x, es_dtype_t dt, const void* xp, int log_domain, double* out,
                     es_stream_t stream);
+/* 1-D Wasserstein-1 distances on the device -- replaces the scipy.stats.wasserstein_distance calls of
+ * calculate_joint_ws_across_experts (train/utils.py:117-176), scipy's _cdf_distance with p = 1 term for term
+ * (fp64; a fixed summation order, bitwise reproducible).
+ * out[s * channels + c] = 1-D Wasserstein-1 distance between column c of the u rows and of the v rows
+ * of segment s.  Segment s covers u rows u_idx[u_seg[2s] .. u_seg[2s+1]) (u_idx NULL: the rows
+ * themselves) and likewise for v; segments may overlap (the joint distribution plus one per expert).
+ * u_seg / v_seg / u_idx / v_idx are DEVICE int32 arrays: no host sync.  u_cap / v_cap: host upper bounds
+ * of any segment's length (grid and workspace sizing).  A segment empty on either side gives 0
+ * (the reference's `continue`, train/utils.py:117-176).
+ * u is [u_rows][u_ld] fp64 (u_ld >= channels), u_idx (when given) has u_rows entries; segment bounds are
+ * clamped to [0, u_rows], a segment's length to u_cap and every row index to [0, u_rows); likewise v.
+ * Values must be finite.  u_cap + v_cap <= ES_WS_LDS_MAX: one launch, each problem sorted in LDS, no
+ * workspace; up to 2^20: global-memory passes over `work` (es_wasserstein_1d_workspace bytes).  Above
+ * that, or with too small a workspace: ES_ERR_ARG and nothing is launched. */
+#define ES_WS_LDS_MAX 8192
+size_t es_wasserstein_1d_workspace(int n_seg, int channels, int u_cap, int v_cap);
+int es_wasserstein_1d(const double* u, int64_t u_ld, int u_rows, const int32_t* u_idx, const int32_t* u_seg,
+                      const double* v, int64_t v_ld, int v_rows, const int32_t* v_idx, const int32_t* v_seg,
+                      int n_seg, int channels, int u_cap, int v_cap, double* out,
+                      void* work, size_t work_bytes, es_stream_t stream);
+/* ES_WS_LDS_MAX of the built library (the largest u_cap + v_cap sorted in LDS) */
+int es_wasserstein_lds_max(void);
 
 /* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
