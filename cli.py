@@ -7,7 +7,8 @@ The reference's CUDA_LAUNCH_BLOCKING / cudnn flags / anomaly detection (cli.py:2
 
 Simulation (conditions in, calorimeter images out; MoEWrapper.simulate) from a saved checkpoint:
     python cli.py -o model.architecture=neutron dataset.input_image_shape=[44,44] model.n_experts=3 \
-        --simulate --checkpoint DIR [--checkpoint-epoch E] (--cond FILE.npy | --num-samples N) --out FILE.npz
+        --simulate --checkpoint DIR [--checkpoint-epoch E] (--cond FILE.npy | --num-samples N) --out FILE.npz \
+        [--features]
 """
 import argparse
 import logging
@@ -36,6 +37,8 @@ def parse_args(args=None):
     g.add_argument("--out", type=str, default=None, help="output .npz (images, expert, sums, cond)")
     g.add_argument("--seed", type=int, default=0, help="seed of the simulation's noise and routing draws")
     g.add_argument("--sim-batch-size", type=int, default=None, help="conditions per chunk")
+    g.add_argument("--features", action="store_true",
+                   help="also write the shower-shape observables: features [N,5], peak [N,2]")
     return p.parse_args(args)
 
 
@@ -74,9 +77,11 @@ def simulate(args):
         from expertsim.utils.synthetic import make_batch
         cond = make_batch(args.num_samples, str(cfg.model.architecture), seed=args.seed)["cond"]
     moe.eval()
-    res = moe.simulate(torch.from_numpy(cond), seed=args.seed, batch_size=args.sim_batch_size, sums=True)
+    res = moe.simulate(torch.from_numpy(cond), seed=args.seed, batch_size=args.sim_batch_size, sums=True,
+                       features=args.features)
+    extra = {k: res[k].cpu().numpy() for k in ("features", "peak")} if args.features else {}
     np.savez(args.out, images=res["images"].cpu().numpy(), expert=res["expert"].cpu().numpy(),
-             sums=res["sums"].cpu().numpy(), cond=cond)
+             sums=res["sums"].cpu().numpy(), cond=cond, **extra)
     logger.info("Simulated %d images (epoch %d checkpoint) -> %s", cond.shape[0], epoch, args.out)
 
 

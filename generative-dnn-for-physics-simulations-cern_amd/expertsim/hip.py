@@ -203,6 +203,7 @@ _SIGS = {
     "es_wasserstein_1d": (C.c_int, [P, I64, C.c_int, P, P, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int, C.c_int,
                                     P, P, C.c_size_t, P]),
     "es_wasserstein_lds_max": (C.c_int, []),
+    "es_image_features": (C.c_int, [P, C.c_int, P, C.c_int, P, P, P]),
 }
 
 # the largest nu + nv es_wasserstein_1d sorts in LDS (ES_WS_LDS_MAX of include/expertsim_hip.h; lib()

@@ -633,7 +633,7 @@ class MoEWrapper(nn.Module):
 
     @torch.no_grad()
     def evaluate_device(self, epoch, y_test, x_test, cfg, *, seed=0, sample_offset=0, routing="sample",
-                        fused=True, graph=True, details=False):
+                        fused=True, graph=True, details=False, features=False):
         """The metrics of evaluate (same keys) from the simulate path, without a host round trip until
         the result: real sums by es_channel_sums, repetition j of the n_calc = min(epoch // 5 + 1, 5) by
         simulate(sums=True) -- j = 0 with simulate's own noise draw, j > 0 with es_randn_dev(seed + j) on
@@ -645,8 +645,19 @@ class MoEWrapper(nn.Module):
         identically (the reference routes once per evaluate call), and the metrics are a function of
         (parameters, inputs, seed, sample_offset): bitwise equal on rerun, whatever torch's global RNG.
         details=True adds the device tensors sums_real [N, 5], sums_gen [R, N, 5], expert [N], ws
-        [R, E + 1, 5].  Like simulate, reads training state and changes none; HIP device only."""
-        from ..train.utils import channel_sums, ws_across_experts_device, ws_summary
+        [R, E + 1, 5].  Like simulate, reads training state and changes none; HIP device only.
+
+        features=True adds the shower-shape metrics (train/utils.py:81-112 calculate_image_features):
+        the real side is image_features(x, log_domain=True), the generated side comes from the same R
+        simulate calls (features=True), the distances from one further ws_across_experts_device call
+        over the five train.utils.FEATURE_NAMES columns with the same expert vector, concatenated with
+        the channel distances on the device so that both cross in the one copy, closed by
+        ws_feature_summary: ws_feat_<name> / ws_feat_std_<name> (mean / std over the repetitions of the
+        joint distance) and ws_feat_<name>_<e> (expert e, mean over the repetitions); details=True adds
+        feat_real [N, 5], feat_gen [R, N, 5], ws_feat [R, E + 1, 5].  The other keys keep their values bit
+        for bit."""
+        from ..train.utils import (FEATURE_NAMES, channel_sums, image_features, ws_across_experts_device,
+                                   ws_feature_summary, ws_summary)
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise hip.HipError("MoEWrapper.evaluate_device runs on the HIP device only (no CPU fallback)")
@@ -655,12 +666,16 @@ class MoEWrapper(nn.Module):
         x = x.reshape(-1, *shape)
         E, nd, N = self.n_experts, self.noise_dim, int(x.shape[0])
         with torch.cuda.device(dev):
-            sums_real = channel_sums(x.to(dev, dtype=torch.float32), log_domain=True)
+            x = x.to(dev, dtype=torch.float32)
+            sums_real = channel_sums(x, log_domain=True)
             cond = torch.as_tensor(y_test).to(device=dev, dtype=torch.float32).contiguous()
             if cond.shape[0] != N:
                 raise ValueError(f"evaluate_device: {cond.shape[0]} conditions for {N} images")
             R = min(epoch // 5 + 1, 5)
             sums_gen = torch.empty(R, N, 5, dtype=torch.float64, device=dev)
+            if features:
+                feat_real, _ = image_features(x, log_domain=True)          # the one upload of x serves both
+                feat_gen = torch.empty(R, N, 5, dtype=torch.float64, device=dev)
             expert = None
             for j in range(R):
                 noise = None
@@ -669,16 +684,33 @@ class MoEWrapper(nn.Module):
                     hip.call("es_randn_dev", hip.ptr(noise), N * nd, (int(seed) + j) & 0xFFFFFFFFFFFFFFFF,
                              self.SIM_NOISE_STREAM, None, 0, int(sample_offset) * nd, hip.stream_ptr())
                 sim = self.simulate(cond, seed=seed, sample_offset=sample_offset, noise=noise, routing=routing,
-                                    sums=True, fused=fused, graph=graph)
+                                    sums=True, fused=fused, graph=graph, features=bool(features))
                 sums_gen[j].copy_(sim["sums"])
+                if features:
+                    feat_gen[j].copy_(sim["features"])
                 if expert is None:
                     expert = sim["expert"]
             ws = ws_across_experts_device(sums_real, sums_gen, expert, E)
-            ws_mean, ws_std, ws_mean_exp, ws_std_exp = ws_summary(ws.cpu().numpy())   # the one D2H copy
+            if features:
+                ws_feat = ws_across_experts_device(feat_real, feat_gen, expert, E)
+                both = torch.stack([ws, ws_feat]).cpu().numpy()                       # the one D2H copy
+                ws_host, ws_feat_host = both[0], both[1]
+            else:
+                ws_host = ws.cpu().numpy()                                            # the one D2H copy
+            ws_mean, ws_std, ws_mean_exp, ws_std_exp = ws_summary(ws_host)
         log = {"ws_mean": ws_mean, **{f"ws_mean_{i}": ws_mean_exp[i] for i in range(E)},
                "ws_std": ws_std, **{f"ws_std_{i}": ws_std_exp[i] for i in range(E)}, "epoch": epoch}
+        if features:
+            f_mean, f_std, f_exp = ws_feature_summary(ws_feat_host)
+            for k, name in enumerate(FEATURE_NAMES):
+                log[f"ws_feat_{name}"] = f_mean[k]
+                log[f"ws_feat_std_{name}"] = f_std[k]
+                for e in range(E):
+                    log[f"ws_feat_{name}_{e}"] = f_exp[e, k]
         if details:
             log.update(sums_real=sums_real, sums_gen=sums_gen, expert=expert, ws=ws)
+            if features:
+                log.update(feat_real=feat_real, feat_gen=feat_gen, ws_feat=ws_feat)
         return log
 
     # ---------------------------------------------------------------------------- simulation
@@ -688,14 +720,17 @@ class MoEWrapper(nn.Module):
 
     @torch.no_grad()
     def simulate(self, cond, *, seed=0, sample_offset=0, noise=None, batch_size=None, domain="photons",
-                 routing="sample", sums=False, fused=True, graph=True):
+                 routing="sample", sums=False, fused=True, graph=True, features=False):
         """Fast simulation: conditions in, calorimeter images out (the reference's routed prediction,
         train/utils.py:208-266 get_predictions_from_experts_results, on the device).
 
         cond [N, cond_dim] -> {"images" [N,H,W] fp32 in the order of cond (photons: expm1 of the
         generator's log1p-domain output; log: that output), "expert" [N] int32, "noise" [N, noise_dim],
-        and with sums=True "sums" [N,5] fp64, the five channel sums of the photon images}, all on the
-        device.  Per chunk of batch_size conditions (default eval_batch_size; the last may be short):
+        and with sums=True "sums" [N,5] fp64, the five channel sums of the photon images, and with
+        features=True "features" [N,5] fp64 (train.utils.FEATURE_NAMES) and "peak" [N,2] int32 (row, col),
+        the shower-shape observables of the images as returned: one es_image_features launch per chunk
+        after the last expert's es_sim_finish, inside the chunk program}, all on the device.  Per chunk of
+        batch_size conditions (default eval_batch_size; the last may be short):
         router forward -> routing ("sample": the stochastic Gumbel at tau = 1 of evaluate / moe.py:650;
         "argmax": argmax of the logits) -> es_router_dispatch, and per expert, serially on the
         current stream, es_gather_rows_at of [noise | cond] with the expert's device count ->
@@ -707,8 +742,8 @@ class MoEWrapper(nn.Module):
         depend on (seed, sample_offset + i) only, not on the chunking or the routing of other samples;
         noise= injects the rows instead.  A rank of a data-parallel job passes its own sample_offset.
         graph=True: the chunk program (router to finish) is captured once per (chunk size, domain, sums,
-        fused, routing) on one stream and replayed; the chunk's cond / noise / Gumbel draws are written
-        into its static input buffers before each replay.
+        fused, routing, features) on one stream and replayed; the chunk's cond / noise / Gumbel draws are
+        written into its static input buffers before each replay.
         Changes no training state: parameters, running statistics, batch counters, step counters and
         optimizers are only read."""
         if domain not in ("photons", "log"):
@@ -730,10 +765,13 @@ class MoEWrapper(nn.Module):
                "noise": torch.empty(N, nd, dtype=torch.float32, device=dev)}
         if sums:
             out["sums"] = torch.empty(N, 5, dtype=torch.float64, device=dev)
+        if features:
+            out["features"] = torch.empty(N, 5, dtype=torch.float64, device=dev)
+            out["peak"] = torch.empty(N, 2, dtype=torch.int32, device=dev)
         set_deterministic(self.precision == "fp32" and self.deterministic)
         set_f32_split(self.fp32_mfma == "split")
         for start, n, roff, eoff in simulate_plan(N, batch_size or self.eval_batch_size, sample_offset, nd, E):
-            key = (n, domain, bool(sums), bool(fused), routing)
+            key = (n, domain, bool(sums), bool(fused), routing, bool(features))
             st = self._sim_state(key, dev, H, W)
             st["cond"].copy_(cond[start:start + n])
             if noise is not None:
@@ -766,6 +804,9 @@ class MoEWrapper(nn.Module):
                 out["expert"][start:start + n].copy_(st["expert"])
             if sums:
                 out["sums"][start:start + n].copy_(st["sums"])
+            if features:
+                out["features"][start:start + n].copy_(st["features"])
+                out["peak"][start:start + n].copy_(st["peak"])
         return out
 
     sim_captures = 0
@@ -787,11 +828,15 @@ class MoEWrapper(nn.Module):
                 "sums": buf((n, 5), torch.float64), "expert": torch.zeros(n, dtype=torch.int32, device=dev),
                 "perm": buf((n,), torch.int32), "offs": buf((E + 1,), torch.int32),
                 "counts": torch.zeros(E, dtype=torch.int32, device=dev), "graph": None}
+            if key[5]:
+                st["features"] = buf((n, 5), torch.float64)
+                st["peak"] = buf((n, 2), torch.int32)
         return st
 
     def _sim_chunk(self, st, key):
-        """One chunk: router, dispatch, per-expert gather / infer / finish (all on the current stream)."""
-        n, domain, sums, fused, _ = key
+        """One chunk: router, dispatch, per-expert gather / infer / finish, then with features the
+        shower-shape pass over the chunk's finished images (all on the current stream)."""
+        n, domain, sums, fused, _, features = key
         E, nd = self.n_experts, self.noise_dim
         photons = 1 if domain == "photons" else 0
         x0 = st["x0"]
@@ -802,7 +847,17 @@ class MoEWrapper(nn.Module):
             h6 = self.generators[0].infer(x0, rows=None, fused=fused)
             hip.call("es_sim_finish", C.byref(h6.view), h6.ptr, None, None, None, photons, hip.ptr(st["images"]),
                      sums_ptr, hip.stream_ptr())
-            return
+        else:
+            self._sim_experts(st, n, photons, sums_ptr, fused)
+        if features:
+            img = st["images"]
+            v = hip.make_view((n, 1, img.shape[1], img.shape[2]), (img.stride(0), 0, img.stride(1), img.stride(2)), False)
+            hip.call("es_image_features", C.byref(v), hip.ES_F32, hip.ptr(img), 0, hip.ptr(st["features"]),
+                     hip.ptr(st["peak"]), hip.stream_ptr())
+
+    def _sim_experts(self, st, n, photons, sums_ptr, fused):
+        """The routed part of a chunk with more than one expert."""
+        E, x0 = self.n_experts, st["x0"]
         _, _, idx, counts, _ = self.router.fwd(st["cond"], st["expo"], 1.0)
         st["expert"].copy_(idx)
         st["counts"].copy_(counts)

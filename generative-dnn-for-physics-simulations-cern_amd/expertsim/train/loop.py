@@ -100,12 +100,21 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     """Reference loop.py:185-256 without the plots: per-batch MoEWrapper.evaluate, averaged.
     train.eval_on_device: MoEWrapper.evaluate_device instead (routing, generation and the Wasserstein
     distances on the device, seeded by train.rng_seed; a sample's draws depend on its position in the
-    test set, not on the loader's batch size)."""
+    test set, not on the loader's batch size).  train.eval_features (with eval_on_device only): also the
+    shower-shape metrics of evaluate_device(features=True), averaged like the others."""
+    on_device = bool(cfg.train.get("eval_on_device", False))
+    features = bool(cfg.train.get("eval_features", False))
+    if features and not on_device:
+        raise ValueError("train.eval_features needs train.eval_on_device: the shower-shape metrics exist on the "
+                         "device path only (MoEWrapper.evaluate_device)")
     moe.eval()
     keys = ["ws_mean", *[f"ws_mean_{i}" for i in range(moe.n_experts)],
             "ws_std", *[f"ws_std_{i}" for i in range(moe.n_experts)]]
+    if features:
+        from .utils import FEATURE_NAMES
+        for name in FEATURE_NAMES:
+            keys += [f"ws_feat_{name}", f"ws_feat_std_{name}", *[f"ws_feat_{name}_{i}" for i in range(moe.n_experts)]]
     acc: Dict[str, List[float]] = {k: [] for k in keys}
-    on_device = bool(cfg.train.get("eval_on_device", False))
     seen = 0                                   # test samples in earlier batches
     for b, batch in enumerate(test_loader):
         if max_batches is not None and b >= max_batches:
@@ -113,7 +122,8 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
         real_images, _, cond, std, intensity, true_positions = batch
         if on_device:
             m = moe.evaluate_device(epoch, cond.to(device), real_images, cfg,
-                                    seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=seen)
+                                    seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=seen,
+                                    features=features)
             seen += int(cond.shape[0])
         else:
             m = moe.evaluate(epoch, cond.to(device), real_images, true_positions, std, intensity, cfg, device)

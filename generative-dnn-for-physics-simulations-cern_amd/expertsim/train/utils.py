@@ -4,6 +4,7 @@ Same names, arguments and return conventions as the reference:
   get_channel_masks(a [H,W])                        train/utils.py:18-59   (host, numpy: geometry only)
   sum_channels_parallel(data [N,H,W])               train/utils.py:62-78   -> zip of 5-tuples
   get_max_value_image_coordinates(img)              train/utils.py:81-82
+  calculate_image_features(images [N,H,W])          train/utils.py:85-112  -> [5, N] float64
   calculate_joint_ws_across_experts(...)            train/utils.py:117-176
   get_predictions_from_generator_results(...)       train/utils.py:179-205
   get_predictions_from_experts_results(...)         train/utils.py:208-266   (routed, device-side dispatch)
@@ -21,6 +22,12 @@ Device evaluation (MoEWrapper.evaluate_device, opt-in): ``wasserstein_1d_device`
 csrc/wasserstein.hip: scipy's arithmetic term for term) from the batch-ordered sums and the expert
 vector; only the [n_calc, E + 1, 5] distances cross to the host, where ``ws_summary`` closes them as
 calculate_joint_ws_across_experts does.
+
+Shower-shape observables: ``image_features`` (es_image_features, csrc/features.hip) reduces every image
+to the five values of calculate_image_features and its peak pixel in one pass on the device;
+``calculate_image_features`` is the reference's API over it, MoEWrapper.simulate(features=True) fuses it
+into the chunk program, and MoEWrapper.evaluate_device(features=True) takes the per-feature Wasserstein
+distances with the same es_wasserstein_1d call, closed by ``ws_feature_summary``.
 """
 from __future__ import annotations
 
@@ -95,6 +102,38 @@ def sum_channels_parallel(data):
 def get_max_value_image_coordinates(img):
     """train/utils.py:81-82 (host helper used by the data pipeline)."""
     return np.unravel_index(np.argmax(img), img.shape)
+
+
+FEATURE_NAMES = ("max_x", "max_y", "center_x", "center_y", "nonzero")
+
+
+def image_features(images, log_domain: bool = False, device=None):
+    """(feat [N,5] fp64, peak [N,2] int32) device tensors of the shower-shape observables of each image
+    (HIP kernel es_image_features, csrc/features.hip; train/utils.py:81-112).
+
+    feat columns, FEATURE_NAMES: the largest column sum, the largest row sum, the centre of the hit mask
+    (pixels > 0) in x and y (w / 2, h / 2 for an image without a hit) and the number of hit pixels; peak:
+    (row, col) of the first maximum in row-major order (get_max_value_image_coordinates).  images as
+    channel_sums takes them; H, W <= 64; no NaN.  log_domain=True describes expm1(images), fused into
+    the same pass with the float32 expm1 of channel_sums."""
+    x = _as_device_images(images, device)
+    N, H, W = x.shape
+    feat = torch.empty(N, 5, dtype=torch.float64, device=x.device)
+    peak = torch.empty(N, 2, dtype=torch.int32, device=x.device)
+    if N == 0:
+        return feat, peak
+    view = hip.make_view((N, 1, H, W), (x.stride(0), H * W, x.stride(1), x.stride(2)))
+    with torch.cuda.device(x.device):
+        hip.call("es_image_features", C.byref(view), hip.dt_of(x), C.c_void_p(x.data_ptr()),
+                 1 if log_domain else 0, hip.ptr(feat), hip.ptr(peak), hip.stream_ptr())
+    return feat, peak
+
+
+def calculate_image_features(images):
+    """Reference API (train/utils.py:85-112): np.ndarray [5, N] float64 with the rows max_values_x,
+    max_values_y, centers_x, centers_y, non_zero_pixels, computed by es_image_features."""
+    feat, _ = image_features(images)
+    return np.ascontiguousarray(feat.cpu().numpy().T)
 
 
 def _generate_log_images(generator, noise: torch.Tensor, cond: torch.Tensor) -> torch.Tensor:
@@ -308,6 +347,19 @@ def ws_summary(ws):
     ws_runs = ws[:, 0].mean(axis=1)
     ws_exp_runs = ws[:, 1:].mean(axis=2)
     return ws_runs.mean(), ws_runs.std(), ws_exp_runs.mean(axis=0), ws_exp_runs.std(axis=0)
+
+
+def ws_feature_summary(ws):
+    """Closing arithmetic of the shower-shape metrics on the host copy of ws_across_experts_device's
+    [R, E + 1, 5] result over the FEATURE_NAMES columns (a pure numpy function): per feature the mean and
+    std over the repetitions of the joint row, and per expert the mean over the repetitions.  Unlike
+    ws_summary nothing is averaged across the columns: a sum of photons, a pixel coordinate and a pixel
+    count differ in scale by orders of magnitude.  Returns (ws_feat [C], ws_feat_std [C],
+    ws_feat_exp [E, C])."""
+    ws = np.asarray(ws, dtype=np.float64)
+    if ws.ndim != 3 or ws.shape[1] < 2:
+        raise ValueError(f"ws_feature_summary: expected [R, E + 1, C], got {ws.shape}")
+    return ws[:, 0].mean(axis=0), ws[:, 0].std(axis=0), ws[:, 1:].mean(axis=0)
 
 
 def calculate_joint_ws_across_experts(n_calc, x_tests: List, y_tests: List, generators: List, ch_org,

@@ -704,6 +704,25 @@ int es_wasserstein_1d(const double* u, int64_t u_ld, int u_rows, const int32_t* 
                       void* work, size_t work_bytes, es_stream_t stream);
 /* ES_WS_LDS_MAX of the built library (the largest u_cap + v_cap sorted in LDS) */
 int es_wasserstein_lds_max(void);
+/* Shower-shape observables of x [n,1,h,w] (any strides, fp32 / bf16) -- calculate_image_features and
+ * get_max_value_image_coordinates (train/utils.py:81-112).  v = the pixel, or the float32 expm1 of it when
+ * log_domain != 0 (the same expm1f as es_channel_sums / es_sim_finish).  feat[b*5 + k] (fp64), in the
+ * reference's row order:
+ *   0 max_x     max over columns j of sum_i v[i,j]     (np.max(np.sum(img, axis=0)))
+ *   1 max_y     max over rows i of sum_j v[i,j]
+ *   2 center_x  mean column index of the pixels with v > 0 (center_of_mass(img > 0)[1]); w / 2 without one
+ *   3 center_y  mean row index of the pixels with v > 0; h / 2 without one
+ *   4 nonzero   number of pixels with v > 0
+ * peak[b*2 .. +1] = (row, col) of the first maximum in row-major order (np.unravel_index(np.argmax(img))).
+ * Values must not be NaN.  Arithmetic (bitwise reproducible, no atomics, independent of n, of the image's
+ * position in the batch and of the strides): each column sum is the fp64 sum over i = 0..h-1 in that
+ * order and each row sum the fp64 sum over j = 0..w-1 in that order, both from +0.0; the index sums and
+ * the count are integers; each centre is one fp64 division.  feat or peak may be NULL (not both).
+ * 1 <= h, w <= 64; outside that, with c != 1, a NULL x / xp or both outputs NULL: ES_ERR_ARG and nothing is
+ * launched.  n == 0: ES_OK without a launch. */
+int es_image_features(const es_view_t* x, es_dtype_t dt, const void* xp, int log_domain,
+                      double* feat /* [n,5] or NULL */, int32_t* peak /* [n,2] or NULL */,
+                      es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
