@@ -1,5 +1,5 @@
 // Shared host/device definitions of the implicit-GEMM convolution kernels (conv_igemm.hip: the
-// generic / register-staged and first LDS-DMA kernels; conv_mfma.hip: the 8-wave LDS-DMA ring
+// generic / register-staged and first LDS-DMA kernels; conv_ring_kernel.h, conv_persist.hip, conv_mfma.hip: the 8-wave LDS-DMA ring
 // kernels).  ConvArgs is passed by value to every conv kernel, so both files see one definition.
 #pragma once
 #include "common.h"
@@ -22,7 +22,7 @@ __device__ __forceinline__ int fdiv(int x, FastDiv f) {
   return (int)((__umulhi((uint32_t)x, f.m) + (uint32_t)x) >> f.l);
 }
 
-// Sub-pixel decomposition of a stride-1 conv over a x2 nearest-upsampled input (conv_mfma.hip).
+// Sub-pixel decomposition of a stride-1 conv over a x2 nearest-upsampled input (conv_ring_host.hip).
 // Output pixels split into 4 parity classes c = 2a + b, (p - pad) mod 2 = a, (q - pad) mod 2 = b.
 // Class c covers output rows p = p0[c] + 2u (u < ph[c]) and is a plain dh[c] x dw[c] conv on the
 // SOURCE grid: y[p0 + 2u][q0 + 2v] = sum_{d,e} x[u + oh + d][v + ow + e] * W'_c[d][e] with
@@ -143,18 +143,18 @@ inline int64_t dgrad_rows(const es_conv_desc_t& d, int n) {
   return (int64_t)n * (d.up_h > 0 ? d.H * d.W : d.Hu * d.Wu);
 }
 
-// the fp32 MFMA arithmetic level of the ring kernels (es_conv_set_f32_split: 0 exact, 1 / 2 split-fp32)
+// the fp32 MFMA arithmetic level of the ring kernels (es_conv_set_f32_split: 0 exact, 2 split-fp32)
 int es_f32_split_level();
 
 // split-fp32 weight planes: byte offset of the planes behind an fp32 packing of n elements
 extern "C" int64_t es_weight_planes_offset(int64_t n);
 
-// 8-wave LDS-DMA ring kernels (conv_mfma.hip).  Return 1 when the call was launched, 0 when the
+// 8-wave LDS-DMA ring kernels (conv_ring_host.hip plans and launches them).  Return 1 when the call was launched, 0 when the
 // shape is not eligible (the caller falls back to the kernels of conv_igemm.hip), <0 on error.
 int es_conv_ring_launch(ConvArgs& a, int mode, ConvCall& call, hipStream_t st);
 // fp32 operands (parity mode): FWD / DGRAD ring kernels over image chunks (same return convention)
 int es_conv_ring_launch_f32(ConvArgs& a, int mode, ConvCall& call, hipStream_t st);
-// deterministic fp32 WGRAD on the ring (conv_mfma.hip): partial floats needed (-1: not eligible), and
+// deterministic fp32 WGRAD on the ring (conv_ring_host.hip, conv_mfma.hip): partial floats needed (-1: not eligible), and
 // the launch (partials in call.det_ws + ordered reduce into the torch-layout dW; 1 done, 0 not eligible,
 // < 0 error)
 int64_t es_wgrad_f32_ring_floats(const es_conv_desc_t& d, const int64_t ys[4], const int64_t xs[4]);

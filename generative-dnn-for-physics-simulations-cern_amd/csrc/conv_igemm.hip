@@ -891,7 +891,7 @@ int launch(ConvArgs& a, bool avec, bool bvec, ConvCall& call, hipStream_t st) {
     }
   }
   if constexpr (sizeof(T) == 4 && MODE != MODE_WGRAD) {
-    // fp32 parity mode: the 8-wave LDS-DMA ring kernels on v_mfma_f32_16x16x4_f32 (conv_mfma.hip)
+    // fp32 parity mode: the 8-wave LDS-DMA ring kernels on v_mfma_f32_16x16x4_f32 (conv_ring_f32.hip)
     // for real convolutions whose K-steps are one tap x 32 channels
     const int nch = MODE == MODE_FWD ? a.d.C : a.d.K;
     // (the gathered grid's pixels per image: >= 8 keeps the row tiles' padding small; the aux
@@ -1164,7 +1164,7 @@ extern "C" int es_conv2d_fwd_stats(const es_conv_desc_t* d, es_dtype_t dt, const
 }
 
 // es_conv2d_fwd with y = act(scale[k] * (acc + bias[k]) + shift[k]) applied before the rounding, when
-// the kernel that runs the conv carries that epilogue (the ring FWD kernels of conv_mfma.hip in bf16
+// the kernel that runs the conv carries that epilogue (the ring FWD kernels of conv_ring_kernel.h in bf16
 // and split-fp32); otherwise y is es_conv2d_fwd's and *fused = 0.
 extern "C" int es_conv2d_fwd_affine(const es_conv_desc_t* d, es_dtype_t dt, const void* x, const int64_t xs[4],
                                     const void* wk, const float* bias, const es_affine_t* epi, void* y,

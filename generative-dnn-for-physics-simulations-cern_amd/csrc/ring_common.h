@@ -1,4 +1,4 @@
-// Device helpers shared by the LDS-DMA ring kernels (conv_mfma.hip) and the wave-specialised
+// Device helpers shared by the LDS-DMA ring kernels (ring_device.h and the files built on it) and the wave-specialised
 // split-fp32 weight gradient (conv_wgrad_ws.hip): buffer resources / LDS-DMA, the raw barrier and
 // counted waits, the XCD-aware workgroup remap.
 #pragma once

@@ -1,4 +1,4 @@
-// Split-fp32 arithmetic on the bf16 MFMA (shared by the ring conv kernels, conv_mfma.hip, and the
+// Split-fp32 arithmetic on the bf16 MFMA (shared by the ring conv kernels, conv_ring_kernel.h and conv_mfma.hip, and the
 // fused discriminator front, d_front2.hip).
 #pragma once
 #include "common.h"

@@ -215,18 +215,17 @@ def deterministic() -> bool:
 
 # fp32 MFMA arithmetic of the ring convolutions: exact fp32 (v_mfma_f32_16x16x4_f32) or split-fp32
 # (three bf16 planes per operand, six plane products on v_mfma_f32_16x16x32_bf16; es_conv_set_f32_split).
-# Level 2 (the level used when on): the packed weights carry their planes (es_pack_weight_planes), so the
-# FWD / DGRAD kernels split only the activations (level 1, both split in the kernel, stays a test hook).
-# The level the C side uses is the single source of truth (es_conv_set_f32_split clamps to {0, 1, 2}),
-# so the Python mirror is read back from C (packing the weight planes must follow the level the kernels run).
+# When on (level 2, the only split level), the packed weights carry their planes (es_pack_weight_planes), so
+# the FWD / DGRAD kernels split only the activations.  The level the C side uses is the single source of
+# truth (es_conv_set_f32_split answers 0 or 2), so the Python mirror is read back from C (packing the weight
+# planes must follow the level the kernels run).
 _F32_SPLIT = None
-_SPLIT_LEVEL = 2
 _LIN_PIX = True      # ConvOp._pixel_view (tests compare it against the plain linear path)
 
 
 def set_f32_split(on: bool):
     global _F32_SPLIT
-    lvl = _SPLIT_LEVEL if on else 0
+    lvl = 2 if on else 0
     if lvl != f32_split_level():
         hip.lib().es_conv_set_f32_split(lvl)
         _F32_SPLIT = None
@@ -409,7 +408,7 @@ class ConvOp:
 
     def subpixel(self, d, dtype) -> bool:
         """Run this x2-upsample conv as 4 parity-class convs on the source grid (ring kernels,
-        conv_mfma.hip; bf16, and fp32 with combined weights summed in fp32, whose rounding is ~1e-7
+        conv_ring_kernel.h; bf16, and fp32 with combined weights summed in fp32, whose rounding is ~1e-7
         relative): es_conv_subpixel_ok decides, the weights are packed in modes 2 / 3."""
         if self.up is None or self.up.factor != (2, 2) or dtype not in (torch.bfloat16, torch.float32):
             return False
@@ -499,7 +498,7 @@ class ConvOp:
 
     def _pixel_view(self, x: Act):
         """A wide linear ([B, C] -> [B, K], K >= 1024) as a 1x1 conv over 16-pixel images of the same
-        memory, NHWC (B/16, C, 16, 1): the ring FWD kernels (conv_mfma.hip) tile rows as (image group,
+        memory, NHWC (B/16, C, 16, 1): the ring FWD kernels (conv_ring_kernel.h) tile rows as (image group,
         pixel), so a linear's 1-pixel images would leave 3/4 of every 256-row tile empty (bf16) or miss
         the fp32 ring (>= 16 output pixels per image) and fall to the register-staged fp32-MFMA GEMM;
         the generators' fc2 (256 -> 21632 neutron, neutron/generator.py:17) is the case.  None when the

@@ -108,22 +108,23 @@ typedef struct {
  * 0 = register-staged kernel.  Both accumulate in the same order (bit-identical results); the
  * switch exists for A/B measurement and tests.  Returns the previous setting. */
 int es_conv_set_glds(int on);
-/* Select the 8-wave LDS-DMA ring kernels (conv_mfma.hip) for the bf16 convs whose K-step is one tap
+/* Select the 8-wave LDS-DMA ring kernels (conv_ring_kernel.h) for the bf16 convs whose K-step is one tap
  * x 64 channels: 1 = on (default), 0 = use the 4-wave kernels.  Returns the previous setting. */
 int es_conv_set_ring(int on);
 /* 256 x 256 ring tiles with 32-deep K-steps for sub-pixel FWD and DGRAD with >= 256 output channels:
  * 1 = on (default), 0 = 256 x 128 tiles (same accumulation order: bit-identical results).
  * Returns the previous setting. */
 int es_conv_set_ring256(int on);
-/* Persistent short-K DGRAD kernel (conv_mfma.hip conv_persist_kernel: generator conv_layers.9's
+/* Persistent short-K DGRAD kernel (conv_persist.hip conv_persist_kernel: generator conv_layers.9's
  * dgrad, <= 8 K-steps of 64 channels, 64 or 128 output columns): 1 = on (default), 0 = the ring
- * kernel (same accumulation order: bit-identical outputs).  Returns the previous setting. */
+ * kernel (same accumulation order: bit-identical outputs).  Only bit 0 of `on` is read.  Returns the
+ * previous setting. */
 int es_conv_set_persist(int on);
-/* Persistent 256 x 256 kernel for the merged sub-pixel FWD (conv_mfma.hip conv_p256_kernel:
+/* Persistent 256 x 256 kernel for the merged sub-pixel FWD (conv_persist.hip conv_p256_kernel:
  * generator conv_layers.0 / .5): 1 = on (default), 0 = the per-tile ring kernel (same accumulation
  * order: bit-identical outputs).  Returns the previous setting. */
 int es_conv_set_p256(int on);
-/* Sub-pixel decomposition of stride-1 convs over a x2 nearest upsample (conv_mfma.hip): 1 = on
+/* Sub-pixel decomposition of stride-1 convs over a x2 nearest upsample (conv_ring_host.hip): 1 = on
  * (default; wgrad uses it internally, fwd/dgrad when the caller packs mode 2/3 weights and sets
  * desc->subpixel), 0 = off.  Returns the previous setting. */
 int es_conv_set_subpixel(int on);
@@ -159,7 +160,7 @@ typedef struct {
  * rounding to ydt (evaluated as one fma with shift' = scale * bias + shift).  Replaces
  * aten::convolution / addmm + the eval-mode aten::native_batch_norm + leaky_relu of
  * neutron/generator.py:13-36 on the simulation path (train/utils.py:179-266).
- * *fused = 1: the kernel that ran applied the epilogue (the ring FWD kernels of conv_mfma.hip, bf16
+ * *fused = 1: the kernel that ran applied the epilogue (the ring FWD kernels of conv_ring_kernel.h / conv_persist.hip, bf16
  * and split-fp32 operands).  *fused = 0: y holds the plain conv + bias output, bit-identical to
  * es_conv2d_fwd, and the caller runs es_norm_act_fwd with the running statistics.
  * d->rows / rows_px as es_conv2d_fwd: images past the live count are neither read nor written. */
@@ -213,14 +214,15 @@ int es_set_deterministic(int on);
  * as the 1 GiB operand limit requires); returns the previous value. */
 int es_conv_set_f32_chunk(int images);
 /* fp32 MFMA arithmetic of the ring convolutions (returns the previous setting): 0 = exact fp32
- * (v_mfma_f32_16x16x4_f32), 1 = split-fp32: each fp32 operand is the exact sum of three bf16
+ * (v_mfma_f32_16x16x4_f32), any other value = split-fp32 (returned as 2): each fp32 operand is the exact sum of three bf16
  * planes and the six plane products with p + q <= 2 run on v_mfma_f32_16x16x32_bf16 into the fp32
  * accumulator (dropped terms < 2^-23 |a b| per product; deterministic, fixed order).  Replaces the
  * same fp32 conv2d / conv_transpose products as es_conv2d_fwd / _dgrad / _wgrad_det (neutron
  * generator.py:23-35, proton generator.py:26-38).  MoEWrapper sets it from train.fp32_mfma. */
 int es_conv_set_f32_split(int on);
-/* on = 2: as 1, and the FWD / DGRAD kernels read the packed weights' bf16 planes precomputed by
- * es_pack_weight_planes (the caller packs them whenever level 2 is set).
+/* Split-fp32 FWD / DGRAD kernels read the packed weights' bf16 planes precomputed by
+ * es_pack_weight_planes (the caller packs them whenever the split mode is set), and split only the
+ * activations themselves.
  * Byte offset of the planes behind an fp32 packing of n elements, and the planes themselves: each
  * 32-element block g of the packing -> 192 bytes at base + es_weight_planes_offset(n) + 192 g, three
  * planes of 32 bf16 (x0 = rne(x), x1 = rne(x - x0), x2 = x - x0 - x1), k-permuted as the ring

@@ -1,7 +1,7 @@
 """fp32 (parity-mode) ring convolutions and the deterministic weight gradient.
 
 The generator convs of the parity mode run on the 8-wave LDS-DMA ring kernels with
-v_mfma_f32_16x16x4_f32 (conv_mfma.hip, ``T = float``), the x2-upsample convs through the sub-pixel
+v_mfma_f32_16x16x4_f32 (conv_ring_f32.hip, ``T = float``), the x2-upsample convs through the sub-pixel
 decomposition (combined weights summed in fp32), and the weight gradients through
 ``es_conv2d_wgrad_det`` (per-split partials + one ordered reduce, no float atomics).
 

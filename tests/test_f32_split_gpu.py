@@ -2,7 +2,7 @@
 
 Every fp32 operand is the exact sum of three bf16 planes (x0 = rne(x), x1 = rne(x - x0),
 x2 = x - x0 - x1) and a product is the sum of the six plane products with p + q <= 2 on
-v_mfma_f32_16x16x32_bf16, accumulated in fp32 (conv_mfma.hip, split8 / mfma_split6).  The dropped
+v_mfma_f32_16x16x32_bf16, accumulated in fp32 (conv_ring_kernel.h / conv_mfma.hip, split8 / mfma_split6).  The dropped
 terms are below 2^-23 |a b| per product, so the result must be as close to the fp64 reference as
 the exact fp32 MFMA result is.
 

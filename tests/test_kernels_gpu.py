@@ -371,7 +371,7 @@ def test_randn_moments():
 
 
 RING_CASES = [
-    # bf16 shapes on the 8-wave ring kernels (conv_mfma.hip); rows not a multiple of the tile
+    # bf16 shapes on the 8-wave ring kernels (conv_ring_kernel.h); rows not a multiple of the tile
     (3, 256, 24, 24, 128, 3, 1, 0, (2, 2)),       # G conv_layers.5: 256x128 FWD, folded DGRAD, WGRAD 128x256
     (7, 128, 13, 13, 256, 3, 1, 0, (2, 2)),       # G conv_layers.0: WGRAD 256x128
     (5, 128, 46, 46, 64, 2, 1, 0, None),          # G conv_layers.9: Ng = 64 tiles
