@@ -1,6 +1,8 @@
-// Shared host/device definitions of the implicit-GEMM convolution kernels (conv_igemm.hip: the
-// generic / register-staged and first LDS-DMA kernels; conv_ring_kernel.h, conv_persist.hip, conv_mfma.hip: the 8-wave LDS-DMA ring
-// kernels).  ConvArgs is passed by value to every conv kernel, so both files see one definition.
+// Shared host/device definitions of the implicit-GEMM convolution kernels (conv_igemm_kernel.h, built in
+// conv_igemm_bf16.hip / conv_igemm_f32.hip: the generic / register-staged and first LDS-DMA kernels;
+// conv_ring_kernel.h, conv_persist.hip, conv_mfma.hip: the 8-wave LDS-DMA ring kernels) and of their host
+// dispatchers (conv_host.hip, conv_ring_host.hip).  ConvArgs is passed by value to every conv kernel, so
+// all of these files see one definition.
 #pragma once
 #include "common.h"
 
@@ -103,7 +105,7 @@ __device__ __forceinline__ int conv_live_px(const ConvArgs& a) {
   return v < 0 ? 0 : v;
 }
 
-// The generic GEMM kernels (conv_igemm.hip) shrink their problem to the live images: M (FWD /
+// The generic GEMM kernels (conv_igemm_kernel.h) shrink their problem to the live images: M (FWD /
 // DGRAD rows, image-major) or the K of a WGRAD (N*P*Q pixels).  mslot keeps the launch's M.
 __device__ __forceinline__ void conv_live_gemm(ConvArgs& a, int mode) {
   a.mslot = a.M;
@@ -150,7 +152,7 @@ int es_f32_split_level();
 extern "C" int64_t es_weight_planes_offset(int64_t n);
 
 // 8-wave LDS-DMA ring kernels (conv_ring_host.hip plans and launches them).  Return 1 when the call was launched, 0 when the
-// shape is not eligible (the caller falls back to the kernels of conv_igemm.hip), <0 on error.
+// shape is not eligible (the caller falls back to the kernels of conv_igemm_kernel.h), <0 on error.
 int es_conv_ring_launch(ConvArgs& a, int mode, ConvCall& call, hipStream_t st);
 // fp32 operands (parity mode): FWD / DGRAD ring kernels over image chunks (same return convention)
 int es_conv_ring_launch_f32(ConvArgs& a, int mode, ConvCall& call, hipStream_t st);

@@ -95,6 +95,7 @@ static int set_switch(T& sw, T v) {
   return old;
 }
 extern "C" int es_conv_set_ring(int on) { return set_switch(g_sw.ring, on != 0); }
+extern "C" int es_conv_set_glds(int on) { return set_switch(g_sw.glds, on != 0); }
 // (bit 0: the persistent short-K DGRAD kernel on / off; the other bits are ignored)
 extern "C" int es_conv_set_persist(int on) { return set_switch(g_sw.persist, (on & 1) != 0); }
 extern "C" int es_conv_set_p256(int on) { return set_switch(g_sw.p256, on != 0); }
@@ -105,6 +106,7 @@ extern "C" int es_conv_set_wgrad_ws(int on) { return set_switch(g_sw.wgrad_ws, o
 // 0: exact fp32; any other value: split-fp32 on pre-split weight planes (level 2, the only split level)
 extern "C" int es_conv_set_f32_split(int on) { return set_switch(g_sw.f32_split, on ? 2 : 0); }
 int es_f32_split_level() { return g_sw.f32_split; }
+const RingSwitches& es_conv_switches() { return g_sw; }
 
 extern "C" int es_subpixel_taps(int R, int S) {
   return (((R - 1) >> 1) + 1 + (R >> 1) + 1) * (((S - 1) >> 1) + 1 + (S >> 1) + 1);

@@ -2,7 +2,7 @@
 // neutron/generator.py:24,29,33 and proton/generator.py:27,33,38 and the aux-regressor convs:
 // everything whose K-step is one filter tap over 64 contiguous channels).
 //
-// Same products as conv_igemm.hip (FWD: y = conv(x, W); DGRAD: dx with the integer upsample
+// Same products as conv_igemm_kernel.h (FWD: y = conv(x, W); DGRAD: dx with the integer upsample
 // folded; WGRAD: dW), re-tiled for gfx950:
 //   * 512 threads = 8 waves, one workgroup per CU (the 3-slot ring takes up to 144 KiB of the
 //     160 KiB LDS), two waves per SIMD, each wave a 64x64 (64x32 / 32x64) tile of

@@ -12,7 +12,8 @@
 
 // es_conv_set_*: test hooks (the kernel tests compare the paths bitwise) and the fp32 arithmetic mode
 struct RingSwitches {
-  bool ring = true;       // es_conv_set_ring(0) routes the bf16 shapes to the 4-wave kernels of conv_igemm.hip
+  bool ring = true;       // es_conv_set_ring(0) routes the bf16 shapes to the 4-wave kernels of conv_igemm_bf16.hip
+  bool glds = true;       // es_conv_set_glds(0) forces the register-staged kernels (tests compare the paths)
   bool subpixel = true;   // es_conv_set_subpixel
   bool ring256 = true;    // es_conv_set_ring256: 256 x 256 tiles
   bool persist = true;    // es_conv_set_persist: the persistent short-K DGRAD
@@ -26,6 +27,8 @@ struct RingSwitches {
   // v_mfma_f32_16x16x32_bf16) with the packed weights' planes precomputed (es_pack_weight_planes)
   int f32_split = 0;
 };
+// the library's switches (conv_ring_host.hip holds them and their setters)
+__attribute__((visibility("hidden"))) const RingSwitches& es_conv_switches();
 
 enum { RK_RING, RK_PERSIST, RK_P256, RK_WGRAD_RING, RK_WGRAD_F32, RK_WGRAD_COL2, RK_WGRAD_COOP };
 
