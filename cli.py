@@ -9,6 +9,11 @@ Simulation (conditions in, calorimeter images out; MoEWrapper.simulate) from a s
     python cli.py -o model.architecture=neutron dataset.input_image_shape=[44,44] model.n_experts=3 \
         --simulate --checkpoint DIR [--checkpoint-epoch E] (--cond FILE.npy | --num-samples N) --out FILE.npz \
         [--features]
+
+Dataset preparation (raw responses + particle conditions in, the three pickles of dataset.source=pickle out;
+expertsim/utils/data_preparation.py) for the detector named by dataset.zdc_type:
+    python cli.py -o dataset.zdc_type=neutron --prepare --images FILE.npy|.pkl --conditions FILE.pkl|.npy \
+        [--cond-columns NAME ...] [--raw] [--min-photon-sum X] [--max-photon-sum X] --out-dir DIR
 """
 import argparse
 import logging
@@ -39,6 +44,18 @@ def parse_args(args=None):
     g.add_argument("--sim-batch-size", type=int, default=None, help="conditions per chunk")
     g.add_argument("--features", action="store_true",
                    help="also write the shower-shape observables: features [N,5], peak [N,2]")
+    d = p.add_argument_group("dataset preparation (instead of training)")
+    d.add_argument("--prepare", action="store_true",
+                   help="compute std, group_number, photon sums and peak positions; write the pickle data source")
+    d.add_argument("--images", type=str, default=None, help=".npy file or pickle of the images [N,H,W]")
+    d.add_argument("--conditions", type=str, default=None,
+                   help="pickle of the conditions frame, or .npy [N,C] matrix named by --cond-columns")
+    d.add_argument("--cond-columns", nargs="*", default=None,
+                   help="column names of a .npy conditions matrix (default: the 9 conditioning columns)")
+    d.add_argument("--raw", action="store_true", help="the images are photon counts: np.log1p is applied first")
+    d.add_argument("--min-photon-sum", type=float, default=None, help="keep samples with photon sum >= this")
+    d.add_argument("--max-photon-sum", type=float, default=None, help="keep samples with photon sum <= this")
+    d.add_argument("--out-dir", type=str, default=None, help="directory for the three pickles")
     return p.parse_args(args)
 
 
@@ -85,10 +102,49 @@ def simulate(args):
     logger.info("Simulated %d images (epoch %d checkpoint) -> %s", cond.shape[0], epoch, args.out)
 
 
+def _load_array_or_pickle(path):
+    import numpy as np
+    import pandas as pd
+    return np.load(path) if path.endswith(".npy") else pd.read_pickle(path)
+
+
+def prepare(args):
+    """--prepare: images + conditions -> the three pickles of the pickle data source."""
+    import numpy as np
+    import pandas as pd
+    import torch
+    from expertsim.config import DEFAULT_PATH, load_config
+    from expertsim.utils import data_preparation as DP
+    if not args.images or not args.conditions or not args.out_dir:
+        raise SystemExit("--prepare needs --images FILE, --conditions FILE and --out-dir DIR")
+    if not torch.cuda.is_available():
+        raise RuntimeError("expertsim prepares datasets on a HIP device only (no CPU fallback)")
+    cfg = load_config(args.config or DEFAULT_PATH, args.override)
+    zdc = str(cfg.dataset.zdc_type)
+    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+    images = np.asarray(_load_array_or_pickle(args.images))
+    if args.raw:
+        images = np.log1p(images.astype(np.float64))
+    cond = _load_array_or_pickle(args.conditions)
+    if not isinstance(cond, pd.DataFrame):
+        cond = pd.DataFrame(np.asarray(cond), columns=args.cond_columns or DP.COND_COLUMNS)
+    images, cond_out, positions = DP.prepare_dataset(images, cond, zdc, args.min_photon_sum, args.max_photon_sum)
+    paths = DP.write_dataset(args.out_dir, zdc, images, cond_out, positions, cfg=cfg)
+    group_col = "group_number_proton" if zdc == "proton" else "group_number"
+    sizes = np.bincount(cond_out[group_col].to_numpy()) if len(cond_out) else np.zeros(0, dtype=np.int64)
+    q = np.percentile(sizes, [25, 50, 75]).tolist() if len(sizes) else [0.0, 0.0, 0.0]
+    logger.info("Prepared %d %s samples in %d groups; group-size quartiles %s (min %d, max %d)", len(cond_out), zdc,
+                len(sizes), q, int(sizes.min()) if len(sizes) else 0, int(sizes.max()) if len(sizes) else 0)
+    logger.info("Wrote %s", " ".join(f"dataset.{k}={v}" for k, v in paths.items()))
+    return paths
+
+
 def main():
     args = parse_args(sys.argv[1:])
     if args.simulate:
         return simulate(args)
+    if args.prepare:
+        return prepare(args)
     from expertsim.config import DEFAULT_PATH, load_config
     from expertsim.train.loop import train
     from expertsim.utils.data_transformations import get_train_test_data_loaders

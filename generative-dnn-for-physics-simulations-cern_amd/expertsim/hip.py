@@ -204,7 +204,14 @@ _SIGS = {
                                     P, P, C.c_size_t, P]),
     "es_wasserstein_lds_max": (C.c_int, []),
     "es_image_features": (C.c_int, [P, C.c_int, P, C.c_int, P, P, P]),
+    "es_group_diversity_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "es_group_diversity": (C.c_int, [P, C.c_int, P, P, P, C.c_int, P, P, P, C.c_size_t, P]),
+    "es_image_sum_peak": (C.c_int, [P, C.c_int, P, P, P, P]),
 }
+
+# es_group_diversity's split of a large group (ES_PREP_SPLIT_MIN / ES_PREP_CHUNKS of include/expertsim_hip.h)
+PREP_SPLIT_MIN = 256
+PREP_CHUNKS = 16
 
 # the largest nu + nv es_wasserstein_1d sorts in LDS (ES_WS_LDS_MAX of include/expertsim_hip.h; lib()
 # checks it against the built library); larger problems take the global-memory passes

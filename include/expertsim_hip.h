@@ -727,6 +727,53 @@ int es_image_features(const es_view_t* x, es_dtype_t dt, const void* xp, int log
                       es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dataset preparation (the reference's notebooks calculating_diversity_for_data,
+ * calculate_and_analysis_of_max_coordinates and data_filtering) -- csrc/prepare.hip.
+ * ---------------------------------------------------------------------------------------- */
+/* SDI-GAN diversity of condition groups over x [n,1,h,w] (any strides; x_f64 = 0: fp32 pixels, 1: fp64
+ * pixels; fp32 is widened exactly, so the results are those of the fp64 arithmetic below on the widened
+ * values).  Group g = the rows perm[offs[g] .. offs[g+1]) -- perm [n] / offs [n_groups + 1] are DEVICE int32
+ * arrays in the layout es_router_dispatch produces: no host sync.  The bounds are clamped to [0, n], every
+ * row index to [0, n).  With n_g the group's member count, per pixel p (fp64, no contraction):
+ *   S = sum_k x[k,p]      over the members in perm order, from +0.0
+ *   m = S / (double)n_g
+ *   Q = sum_k d*d, d = x[k,p] - m   same order, from +0.0; the product is rounded, then added
+ *   var = Q / (double)n_g           (the population variance, ddof = 0)      sd = sqrt(var)
+ * n_g <= ES_PREP_SPLIT_MIN: both sums are one sequential chain.  Above: the members are cut into
+ * ES_PREP_CHUNKS chunks [c L, min(n_g, (c+1) L)), L = ceil(n_g / ES_PREP_CHUNKS); each chunk is summed
+ * sequentially from +0.0 and the chunk sums are added in chunk order from +0.0 (S and Q alike) -- a
+ * function of n_g only.
+ * group_sum[g] = sum_p sd[p] in this order, a function of h*w only: the pixels are cut into tiles of 128
+ * (row-major pixel index; the last tile is padded with +0.0); inside a tile a[i] = sd[2i] + sd[2i+1],
+ * i = 0..63, and the 64 values are combined by six butterfly steps a[i] <- a[i] + a[i ^ o],
+ * o = 32, 16, 8, 4, 2, 1; the tile sums are
+ * then added in tile order from +0.0.  An empty group gives var = 0 and group_sum = +0.0; a one-member
+ * group gives exactly +0.0.  pix_var (optional) receives var per (group, pixel).
+ * Bitwise reproducible; no float atomics; a group's result does not depend on n, on the other groups, on
+ * the strides or on how many workgroups ran.  Values must be finite.
+ * work: es_group_diversity_workspace(n_groups, h, w) bytes.  1 <= h*w <= 4096 and c == 1; outside that,
+ * with a NULL x / xp / perm / offs / group_sum, x_f64 not 0 or 1, or too small a workspace: ES_ERR_ARG and
+ * nothing is launched.  n == 0 or n_groups == 0: ES_OK without a launch. */
+#define ES_PREP_SPLIT_MIN 256
+#define ES_PREP_CHUNKS 16
+size_t es_group_diversity_workspace(int n_groups, int h, int w);
+int es_group_diversity(const es_view_t* x, int x_f64, const void* xp, const int32_t* perm,
+                       const int32_t* offs, int n_groups, double* group_sum /* [G] */,
+                       double* pix_var /* [G, h*w] or NULL */, void* work, size_t work_bytes,
+                       es_stream_t stream);
+/* Photon sum and peak of each image of x [n,1,h,w] (any strides, x_f64 as above):
+ * sum[b] (fp64) = the sum of the image in this order: lane l of 64 adds the pixels with row-major index
+ * l, l + 64, l + 128, .. in that order from +0.0, and the 64 lane sums are combined by the butterfly
+ * a[i] <- a[i] + a[i ^ o], o = 32, 16, 8, 4, 2, 1 (np.sum of the image within h*w 2^-53 relative for
+ * non-negative pixels).  peak[b*2 .. +1] = (row, col) of the first maximum in row-major order, compared in
+ * the input's own precision (np.unravel_index(np.argmax(img), (h, w)); the reference's max_x is the row).
+ * Values must be finite.  sum or peak may be NULL (not both).  1 <= h*w <= 4096 and c == 1; outside that,
+ * with a NULL x / xp, both outputs NULL or x_f64 not 0 or 1: ES_ERR_ARG and nothing is launched.
+ * n == 0: ES_OK without a launch. */
+int es_image_sum_peak(const es_view_t* x, int x_f64, const void* xp, double* sum /* [n] or NULL */,
+                      int32_t* peak /* [n, 2] or NULL */, es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
  * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
  * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
