@@ -14,6 +14,11 @@ Dataset preparation (raw responses + particle conditions in, the three pickles o
 expertsim/utils/data_preparation.py) for the detector named by dataset.zdc_type:
     python cli.py -o dataset.zdc_type=neutron --prepare --images FILE.npy|.pkl --conditions FILE.pkl|.npy \
         [--cond-columns NAME ...] [--raw] [--min-photon-sum X] [--max-photon-sum X] --out-dir DIR
+
+Expert diagnostics (MoEWrapper.diagnose: per-expert histograms and kernel density estimates of the photon
+sums and the conditioning variables, as arrays) from a saved checkpoint:
+    python cli.py -o model.n_experts=3 --diagnose --checkpoint DIR [--checkpoint-epoch E] \
+        --conditions FILE.npy|.pkl --out FILE.npz
 """
 import argparse
 import logging
@@ -44,6 +49,9 @@ def parse_args(args=None):
     g.add_argument("--sim-batch-size", type=int, default=None, help="conditions per chunk")
     g.add_argument("--features", action="store_true",
                    help="also write the shower-shape observables: features [N,5], peak [N,2]")
+    x = p.add_argument_group("expert diagnostics (instead of training)")
+    x.add_argument("--diagnose", action="store_true",
+                   help="per-expert histograms and KDEs for --conditions FILE from --checkpoint DIR, written to --out")
     d = p.add_argument_group("dataset preparation (instead of training)")
     d.add_argument("--prepare", action="store_true",
                    help="compute std, group_number, photon sums and peak positions; write the pickle data source")
@@ -59,20 +67,16 @@ def parse_args(args=None):
     return p.parse_args(args)
 
 
-def simulate(args):
-    """--simulate: load the checkpoint, run MoEWrapper.simulate(sums=True), write the .npz."""
+def _load_checkpointed_moe(args, flag):
+    """(cfg, moe in eval mode, epoch) for --simulate / --diagnose: the model of the config with the
+    checkpoint's weights."""
     import glob
     import re
-    import numpy as np
     import torch
     from expertsim.config import DEFAULT_PATH, load_config
     from expertsim.train.loop import setup_moe_system
     from expertsim.train.training_setup import setup_optimizers
     from expertsim.train.training_utils import load_checkpoint
-    if not args.checkpoint or not args.out or (args.cond is None) == (args.num_samples is None):
-        raise SystemExit("--simulate needs --checkpoint DIR, --out FILE.npz and one of --cond FILE.npy / --num-samples N")
-    if not torch.cuda.is_available():
-        raise RuntimeError("expertsim simulates on a HIP device only (no CPU fallback)")
     cfg = load_config(args.config or DEFAULT_PATH, args.override)
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)
@@ -85,9 +89,22 @@ def simulate(args):
         found = [int(m.group(1)) for f in glob.glob(os.path.join(ckpt, "router_network_epoch_*.pth"))
                  for m in [re.search(r"_epoch_(\d+)\.pth$", f)] if m]
         if not found:
-            raise SystemExit(f"--simulate: no checkpoint files in {ckpt}")
+            raise SystemExit(f"{flag}: no checkpoint files in {ckpt}")
         epoch = max(found)
     load_checkpoint(ckpt, epoch, moe, *setup_optimizers(moe, cfg), None, device)
+    moe.eval()
+    return cfg, moe, epoch
+
+
+def simulate(args):
+    """--simulate: load the checkpoint, run MoEWrapper.simulate(sums=True), write the .npz."""
+    import numpy as np
+    import torch
+    if not args.checkpoint or not args.out or (args.cond is None) == (args.num_samples is None):
+        raise SystemExit("--simulate needs --checkpoint DIR, --out FILE.npz and one of --cond FILE.npy / --num-samples N")
+    if not torch.cuda.is_available():
+        raise RuntimeError("expertsim simulates on a HIP device only (no CPU fallback)")
+    cfg, moe, epoch = _load_checkpointed_moe(args, "--simulate")
     if args.cond is not None:
         cond = np.load(args.cond).astype(np.float32)
     else:
@@ -100,6 +117,30 @@ def simulate(args):
     np.savez(args.out, images=res["images"].cpu().numpy(), expert=res["expert"].cpu().numpy(),
              sums=res["sums"].cpu().numpy(), cond=cond, **extra)
     logger.info("Simulated %d images (epoch %d checkpoint) -> %s", cond.shape[0], epoch, args.out)
+
+
+def diagnose(args):
+    """--diagnose: load the checkpoint, run MoEWrapper.diagnose over the conditions, write the .npz."""
+    import numpy as np
+    import torch
+    from expertsim.train.diagnostics import save_diagnostics
+    if not args.checkpoint or not args.conditions or not args.out:
+        raise SystemExit("--diagnose needs --checkpoint DIR, --conditions FILE and --out FILE.npz")
+    if not torch.cuda.is_available():
+        raise RuntimeError("expertsim computes the diagnostics on a HIP device only (no CPU fallback)")
+    cfg, moe, epoch = _load_checkpointed_moe(args, "--diagnose")
+    cond = _load_array_or_pickle(args.conditions)
+    names = args.cond_columns
+    if hasattr(cond, "columns"):
+        from expertsim.utils.data_transformations import COND_COLUMNS
+        names = names or [c for c in COND_COLUMNS if c in cond.columns]
+        cond = cond[names].to_numpy()
+    cond = np.asarray(cond, dtype=np.float32)
+    diag = moe.diagnose(torch.from_numpy(cond), seed=args.seed, names=names)
+    path = save_diagnostics(args.out, diag)
+    logger.info("Diagnostics of %d conditions over %d experts (epoch %d checkpoint) -> %s", cond.shape[0],
+                moe.n_experts, epoch, path)
+    return path
 
 
 def _load_array_or_pickle(path):
@@ -145,6 +186,8 @@ def main():
         return simulate(args)
     if args.prepare:
         return prepare(args)
+    if args.diagnose:
+        return diagnose(args)
     from expertsim.config import DEFAULT_PATH, load_config
     from expertsim.train.loop import train
     from expertsim.utils.data_transformations import get_train_test_data_loaders

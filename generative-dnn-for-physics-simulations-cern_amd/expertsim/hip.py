@@ -207,11 +207,37 @@ _SIGS = {
     "es_group_diversity_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "es_group_diversity": (C.c_int, [P, C.c_int, P, P, P, C.c_int, P, P, P, C.c_size_t, P]),
     "es_image_sum_peak": (C.c_int, [P, C.c_int, P, P, P, P]),
+    "es_segment_histogram_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "es_segment_histogram": (C.c_int, [P, C.c_int, I64, C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       P, P, P, P, P, C.c_size_t, P]),
+    "es_segment_kde_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "es_segment_kde": (C.c_int, [P, C.c_int, I64, C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, C.c_int,
+                                 C.c_double, P, P, P, P, P, P, C.c_size_t, P]),
 }
 
 # es_group_diversity's split of a large group (ES_PREP_SPLIT_MIN / ES_PREP_CHUNKS of include/expertsim_hip.h)
 PREP_SPLIT_MIN = 256
 PREP_CHUNKS = 16
+
+# expert diagnostics (ES_DIAG_* of include/expertsim_hip.h): the limits of es_segment_histogram / es_segment_kde,
+# the member chunk of the KDE's fixed summation order and the head of both workspaces
+DIAG_MAX_COLS = 64
+DIAG_HIST_MAX_CELLS = 5120
+DIAG_KDE_CHUNK = 256
+DIAG_KDE_MAX_POINTS = 1024
+DIAG_RANGE_BYTES = 1024
+
+
+def segment_histogram_workspace(cols: int, bins: int) -> int:
+    """Bytes of es_segment_histogram's workspace (the column ranges; 0: outside the limits)."""
+    return int(lib().es_segment_histogram_workspace(int(cols), int(bins)))
+
+
+def segment_kde_workspace(n_seg: int, cols: int, points: int, seg_cap: int) -> int:
+    """Bytes of es_segment_kde's workspace: the column ranges and the chunk sums
+    [n_seg][cols][ceil(seg_cap / DIAG_KDE_CHUNK)][points] fp64 (0: outside the limits)."""
+    return int(lib().es_segment_kde_workspace(int(n_seg), int(cols), int(points), int(seg_cap)))
+
 
 # the largest nu + nv es_wasserstein_1d sorts in LDS (ES_WS_LDS_MAX of include/expertsim_hip.h; lib()
 # checks it against the built library); larger problems take the global-memory passes

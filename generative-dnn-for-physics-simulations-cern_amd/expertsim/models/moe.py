@@ -713,6 +713,31 @@ class MoEWrapper(nn.Module):
                 log.update(feat_real=feat_real, feat_gen=feat_gen, ws_feat=ws_feat)
         return log
 
+    @torch.no_grad()
+    def diagnose(self, cond, *, seed=0, sample_offset=0, routing="sample", fused=True, graph=True, bins=50,
+                 points=100, names=None):
+        """Expert-specialisation diagnostics of the routed simulation of cond [N, cond_dim] (the last
+        variable categorical): the dict of train.diagnostics.expert_diagnostics as host numpy arrays --
+        per expert the sample count, the histogram of the generated images' photon sums, the histogram and
+        the Gaussian KDE of every conditioning variable and the counts per value of the categorical one.
+
+        simulate(cond, domain="photons") with the same seed semantics gives the images and the expert
+        vector (that of evaluate_device for the same (seed, sample_offset)); es_image_sum_peak gives the
+        photon sums; es_segment_histogram / es_segment_kde the rest.  Like simulate, reads training state
+        and changes none; HIP device only."""
+        from ..train.diagnostics import expert_diagnostics
+        from ..utils.data_preparation import photon_sums_and_peaks
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise hip.HipError("MoEWrapper.diagnose runs on the HIP device only (no CPU fallback)")
+        with torch.cuda.device(dev):
+            cond = torch.as_tensor(cond).to(device=dev, dtype=torch.float32).contiguous()
+            sim = self.simulate(cond, seed=seed, sample_offset=sample_offset, domain="photons", routing=routing,
+                                fused=fused, graph=graph)
+            photon_sum, _ = photon_sums_and_peaks(sim["images"], check=False)
+            return expert_diagnostics(cond, sim["expert"], self.n_experts, photon_sum, names=names, bins=bins,
+                                      points=points)
+
     # ---------------------------------------------------------------------------- simulation
     # Philox stream ids of the simulation draws (DeviceRNG's step streams start at 1 << 24)
     SIM_NOISE_STREAM = 0x51D00001

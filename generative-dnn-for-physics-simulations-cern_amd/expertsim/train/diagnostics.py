@@ -1,0 +1,230 @@
+"""Expert-specialisation diagnostics on the device -- the numbers behind the reference's plots
+(train/loop.py:234-329, train/utils.py:470-620 plot_expert_heatmap / plot_expert_specialization,
+utils/utils_eval.py:44-51 plot_proton_photonsum_histograms_shared), computed where the conditions, the routing
+and the images already are.  Nothing is drawn: the results are arrays.
+
+Two HIP kernels (csrc/diagnostics.hip, defined in include/expertsim_hip.h):
+
+* ``es_segment_histogram``  per (segment, column) bin counts with numpy's (``right=False``:
+  ``np.histogram(x, bins=e)``) or pandas' (``right=True``: ``pd.cut(x, bins=e, include_lowest=True)``) binning,
+  exactly; the edges are the caller's or ``np.linspace(min, max, bins + 1)`` of each column over all rows.
+* ``es_segment_kde``  per (segment, column) ``scipy.stats.gaussian_kde(d, bw_method='scott')`` on a grid, fp64,
+  in a fixed summation order; pairs with fewer than ``min_samples`` members or a standard deviation below
+  ``std_eps`` are flagged invalid and their density is NaN (the reference skips them).
+
+A segment is an expert's samples: one ``es_router_dispatch`` turns the expert vector into perm / offs and the
+kernels read the rows through perm (no gather copy).  There is no CPU fallback: without a HIP device the
+functions raise hip.HipError.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import hip
+
+
+def _values(values, device=None) -> torch.Tensor:
+    """[N, C] fp32 / fp64 on the device with unit column stride (a 1-D input is one column; other dtypes widen
+    to fp64; host data is copied)."""
+    if not torch.cuda.is_available():
+        raise hip.HipError("expert diagnostics need a HIP device (no CPU fallback)")
+    t = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.asarray(values))
+    if t.dim() == 1:
+        t = t[:, None]
+    if t.dim() != 2:
+        raise ValueError(f"values must be [N] or [N, C], got {tuple(t.shape)}")
+    if t.dtype not in (torch.float32, torch.float64):
+        t = t.double()
+    if not t.is_cuda:
+        t = t.to(torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device()))
+    if t.shape[0] > 1 and (t.stride(0) < t.shape[1] or (t.shape[1] > 1 and t.stride(1) != 1)):
+        t = t.contiguous()
+    return t
+
+
+def _ld(x) -> int:
+    return int(x.stride(0)) if x.shape[0] > 1 else max(int(x.stride(0)), int(x.shape[1]))
+
+
+def _check_segments(x, seg, idx):
+    if seg.dtype != torch.int32 or seg.device != x.device or seg.numel() % 2 or not seg.is_contiguous():
+        raise ValueError("seg must be a contiguous device int32 [n_seg, 2] tensor")
+    if idx is not None and (idx.dtype != torch.int32 or idx.device != x.device or not idx.is_contiguous()
+                            or idx.numel() != x.shape[0]):
+        raise ValueError(f"idx must be a contiguous device int32 [{x.shape[0]}] tensor")
+    return seg.numel() // 2
+
+
+def segment_histogram_raw(x, seg, idx=None, seg_cap=None, bins=50, right=False, edges=None, cols=None):
+    """es_segment_histogram on device tensors: x [N, >= cols] fp32 / fp64 (unit column stride, any row stride),
+    seg [n_seg, 2] int32 bounds of positions in idx (int32 [N]; None: the rows themselves), seg_cap a host upper
+    bound of a segment's length (default N), edges [cols, bins + 1] fp64 or None (np.linspace of each column's
+    range over all N rows).  Returns (counts [n_seg, cols, bins] int32, edges [cols, bins + 1] fp64,
+    outside [n_seg, cols] int32).  No host synchronisation; runs on the current stream."""
+    hip.require_device(x)
+    N = int(x.shape[0])
+    cols = int(x.shape[1]) if cols is None else int(cols)
+    bins = int(bins)
+    S = _check_segments(x, seg, idx)
+    counts = torch.zeros(S, cols, max(bins, 0), dtype=torch.int32, device=x.device)
+    outside = torch.zeros(S, cols, dtype=torch.int32, device=x.device)
+    edges_out = torch.zeros(cols, max(bins, 0) + 1, dtype=torch.float64, device=x.device)
+    if edges is not None:
+        edges = torch.as_tensor(edges).to(device=x.device, dtype=torch.float64).contiguous()
+        if tuple(edges.shape) != (cols, bins + 1):
+            raise ValueError(f"edges must be [{cols}, {bins + 1}], got {tuple(edges.shape)}")
+        if N == 0 or S == 0:
+            edges_out.copy_(edges)
+    with torch.cuda.device(x.device):
+        need = hip.segment_histogram_workspace(cols, bins)
+        work = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+        hip.call("es_segment_histogram", hip.ptr(x), 1 if x.dtype == torch.float64 else 0, _ld(x), N, cols,
+                 hip.ptr(idx), hip.ptr(seg), S, int(seg_cap) if seg_cap is not None else max(N, 1), bins,
+                 1 if right else 0, hip.ptr(edges), hip.ptr(edges_out), hip.ptr(counts), hip.ptr(outside),
+                 hip.ptr(work), need, hip.stream_ptr())
+    return counts, edges_out, outside
+
+
+def segment_kde_raw(x, seg, idx=None, seg_cap=None, points=100, grid=None, min_samples=5, std_eps=1e-12, cols=None):
+    """es_segment_kde on device tensors (arguments as segment_histogram_raw; grid [cols, points] fp64 or None:
+    np.linspace of each column's range over all N rows, a constant column widened by 1e-6 either side).
+    Returns {"density" [n_seg, cols, points], "grid" [cols, points], "bw" [n_seg, cols], "sd" [n_seg, cols]
+    (fp64), "valid" [n_seg, cols] (int32)}; an invalid pair has a NaN density row and bw = sd = 0.  No host
+    synchronisation; runs on the current stream."""
+    hip.require_device(x)
+    N = int(x.shape[0])
+    cols = int(x.shape[1]) if cols is None else int(cols)
+    points = int(points)
+    S = _check_segments(x, seg, idx)
+    dev = x.device
+    density = torch.full((S, cols, max(points, 0)), float("nan"), dtype=torch.float64, device=dev)
+    bw = torch.zeros(S, cols, dtype=torch.float64, device=dev)
+    sd = torch.zeros(S, cols, dtype=torch.float64, device=dev)
+    valid = torch.zeros(S, cols, dtype=torch.int32, device=dev)
+    grid_out = torch.zeros(cols, max(points, 0), dtype=torch.float64, device=dev)
+    if grid is not None:
+        grid = torch.as_tensor(grid).to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(grid.shape) != (cols, points):
+            raise ValueError(f"grid must be [{cols}, {points}], got {tuple(grid.shape)}")
+        if N == 0 or S == 0:
+            grid_out.copy_(grid)
+    cap = int(seg_cap) if seg_cap is not None else max(N, 1)
+    with torch.cuda.device(dev):
+        need = hip.segment_kde_workspace(S, cols, points, min(cap, max(N, 1))) if S > 0 else 0
+        work = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        hip.call("es_segment_kde", hip.ptr(x), 1 if x.dtype == torch.float64 else 0, _ld(x), N, cols, hip.ptr(idx),
+                 hip.ptr(seg), S, cap, points, hip.ptr(grid), int(min_samples), float(std_eps), hip.ptr(grid_out),
+                 hip.ptr(density), hip.ptr(bw), hip.ptr(valid), hip.ptr(sd), hip.ptr(work), need, hip.stream_ptr())
+    return {"density": density, "grid": grid_out, "bw": bw, "sd": sd, "valid": valid}
+
+
+def expert_segments(expert, n_experts: int, n_rows: int, device):
+    """(seg [E, 2] int32, perm int32 [N] or None, offs int32 [E + 1] or None) on the device: expert e's samples
+    are perm[seg[e, 0] .. seg[e, 1]), in batch order -- one es_router_dispatch, as ws_across_experts_device
+    does it.  expert None: one segment over all rows, no perm."""
+    E, N = int(n_experts), int(n_rows)
+    if expert is None:
+        if E != 1:
+            raise ValueError(f"n_experts = {E} needs an expert vector")
+        return torch.tensor([[0, N]], dtype=torch.int32, device=device), None, None
+    if tuple(expert.shape) != (N,):
+        raise ValueError(f"expert must be [{N}], got {tuple(expert.shape)}")
+    expert = expert.to(device=device, dtype=torch.int32).contiguous()
+    perm = torch.empty(N, dtype=torch.int32, device=device)
+    offs = torch.zeros(E + 1, dtype=torch.int32, device=device)
+    if N > 0:
+        with torch.cuda.device(device):
+            hip.call("es_router_dispatch", hip.ptr(expert), N, E, hip.ptr(perm), hip.ptr(offs), hip.stream_ptr())
+    seg = torch.stack([offs[:-1], offs[1:]], dim=1).contiguous()
+    return seg, perm, offs
+
+
+def segment_histogram(values, expert=None, n_experts=1, bins=50, right=False, edges=None):
+    """Per expert and per column of values [N, C] (or [N]) the bin counts: (counts [E, C, bins] int32,
+    edges [C, bins + 1] fp64, outside [E, C] int32), device tensors.  right=False is np.histogram's binning,
+    right=True pd.cut(include_lowest=True)'s; edges None: np.linspace(min, max, bins + 1) per column over all
+    N samples.  expert [N] int32 (None: one segment over all samples)."""
+    x = _values(values)
+    seg, perm, _ = expert_segments(expert, n_experts, x.shape[0], x.device)
+    return segment_histogram_raw(x, seg, perm, None, bins, right, edges)
+
+
+def segment_kde(values, expert=None, n_experts=1, points=100, grid=None, min_samples=5, std_eps=1e-12):
+    """Per expert and per column of values [N, C] (or [N]) the Gaussian KDE with Scott's bandwidth on a grid of
+    `points` values (grid None: np.linspace(min, max, points) per column over all N samples): the dict of
+    segment_kde_raw, device tensors."""
+    x = _values(values)
+    seg, perm, _ = expert_segments(expert, n_experts, x.shape[0], x.device)
+    return segment_kde_raw(x, seg, perm, None, points, grid, min_samples, std_eps)
+
+
+DIAGNOSTIC_KEYS = ("expert_count", "photon_sum_hist", "photon_sum_edges", "cond_hist", "cond_edges", "cond_kde",
+                   "cond_kde_grid", "cond_kde_bw", "cond_kde_valid", "cat_values", "cat_count")
+
+
+def expert_diagnostics(cond, expert, n_experts, photon_sum, names=None, bins=50, points=100):
+    """The numeric content of the reference's specialisation plots as host numpy arrays.  cond [N, C]
+    (C - 1 continuous variables, then one categorical), expert [N] int32, photon_sum [N]; E = n_experts:
+
+      expert_count     [E]               samples routed to each expert
+      photon_sum_hist  [E, bins]         np.histogram binning over the range of all samples
+      photon_sum_edges [bins + 1]
+      cond_hist        [E, C, bins]      pd.cut(include_lowest=True) binning per conditioning variable
+      cond_edges       [C, bins + 1]
+      cond_kde         [E, C - 1, points]  Gaussian KDE (Scott) of the continuous variables; NaN where invalid
+      cond_kde_grid    [C - 1, points]
+      cond_kde_bw      [E, C - 1]
+      cond_kde_valid   [E, C - 1]        0: fewer than 5 samples or a standard deviation below 1e-12
+      cat_values       [K]               distinct values of the last variable
+      cat_count        [E, K]            samples per expert and distinct value
+      cond_names       [C]               only with names
+
+    One es_router_dispatch serves every kernel call.  torch.unique on the last variable is the one place that
+    synchronises before the end (K sizes a tensor); everything crosses to the host in one copy."""
+    c = _values(cond)
+    N, C = int(c.shape[0]), int(c.shape[1])
+    E = int(n_experts)
+    dev = c.device
+    if C < 2:
+        raise ValueError(f"expert_diagnostics: {C} conditioning variables (at least one continuous and the categorical)")
+    if names is not None and len(names) != C:
+        raise ValueError(f"expert_diagnostics: {len(names)} names for {C} conditioning variables")
+    ps = _values(photon_sum)
+    if tuple(ps.shape) != (N, 1):
+        raise ValueError(f"expert_diagnostics: photon_sum {tuple(ps.shape)} for {N} conditions")
+    if expert is None:
+        expert = torch.zeros(N, dtype=torch.int32, device=dev)
+    seg, perm, offs = expert_segments(expert, E, N, dev)
+    ps_hist, ps_edges, _ = segment_histogram_raw(ps, seg, perm, None, bins, False)
+    c_hist, c_edges, _ = segment_histogram_raw(c, seg, perm, None, bins, True)
+    kde = segment_kde_raw(c, seg, perm, None, points, cols=C - 1)
+    cat_values, codes = torch.unique(c[:, C - 1], return_inverse=True)
+    K = int(cat_values.numel())
+    cat_edges = (torch.arange(K + 1, dtype=torch.float64, device=dev) - 0.5)[None]
+    cat_count, _, _ = segment_histogram_raw(codes.to(torch.float64)[:, None], seg, perm, None, max(K, 1), False,
+                                            cat_edges if K > 0 else None)
+    parts = {"expert_count": (offs[1:] - offs[:-1]), "photon_sum_hist": ps_hist[:, 0], "photon_sum_edges": ps_edges[0],
+             "cond_hist": c_hist, "cond_edges": c_edges, "cond_kde": kde["density"], "cond_kde_grid": kde["grid"],
+             "cond_kde_bw": kde["bw"], "cond_kde_valid": kde["valid"], "cat_values": cat_values,
+             "cat_count": cat_count[:, 0, :K]}
+    flat = torch.cat([parts[k].reshape(-1).to(torch.float64) for k in DIAGNOSTIC_KEYS]).cpu().numpy()   # the one copy
+    out, at = {}, 0
+    for k in DIAGNOSTIC_KEYS:
+        n = parts[k].numel()
+        a = flat[at:at + n].reshape(tuple(parts[k].shape))
+        at += n
+        integer = k in ("expert_count", "photon_sum_hist", "cond_hist", "cond_kde_valid", "cat_count")
+        out[k] = a.astype(np.int64) if integer else a.copy()
+    if names is not None:
+        out["cond_names"] = np.asarray([str(n) for n in names])
+    return out
+
+
+def save_diagnostics(path, diag) -> str:
+    """Write the dict of expert_diagnostics as an .npz; returns the path written."""
+    path = str(path)
+    if not path.endswith(".npz"):
+        path += ".npz"
+    np.savez(path, **{k: np.asarray(v) for k, v in diag.items()})
+    return path

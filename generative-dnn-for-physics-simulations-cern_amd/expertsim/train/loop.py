@@ -8,7 +8,8 @@ every rank trains on its own shard and gradients are all-reduced over RCCL (expe
 HIP path, or with ``train.eval_on_device`` those of
 MoEWrapper.evaluate_device (everything up to the distances on the device).  Checkpoints (hooks.CheckpointSaver, training_utils) and the
 EMAHelper (ema.py) follow loop.py:36-107,357-418; resume restores weights, optimizer moments and
-the step counters.  Plotting and W&B stay out of scope.
+the step counters.  W&B and the drawing of figures stay out of scope; the numbers behind the reference's
+expert-specialisation plots are ``train.eval_diagnostics`` (MoEWrapper.diagnose, train/diagnostics.py).
 """
 from __future__ import annotations
 
@@ -101,9 +102,18 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     train.eval_on_device: MoEWrapper.evaluate_device instead (routing, generation and the Wasserstein
     distances on the device, seeded by train.rng_seed; a sample's draws depend on its position in the
     test set, not on the loader's batch size).  train.eval_features (with eval_on_device only): also the
-    shower-shape metrics of evaluate_device(features=True), averaged like the others."""
+    shower-shape metrics of evaluate_device(features=True), averaged like the others.
+    train.eval_diagnostics (with eval_on_device only): after the last batch, MoEWrapper.diagnose once over
+    the conditions of the whole test set (the reference concatenates the test set for its specialisation
+    plots, loop.py:234-329) with seed = train.rng_seed and sample_offset = 0, under
+    metrics["expert_diagnostics"]; with train.save_experiment_data and train.dir_info also written to
+    diagnostics_epoch_<epoch>.npz there.  Off: the returned dict and the launches are unchanged."""
     on_device = bool(cfg.train.get("eval_on_device", False))
     features = bool(cfg.train.get("eval_features", False))
+    diagnostics = bool(cfg.train.get("eval_diagnostics", False))
+    if diagnostics and not on_device:
+        raise ValueError("train.eval_diagnostics needs train.eval_on_device: the expert diagnostics exist on the "
+                         "device path only (MoEWrapper.diagnose)")
     if features and not on_device:
         raise ValueError("train.eval_features needs train.eval_on_device: the shower-shape metrics exist on the "
                          "device path only (MoEWrapper.evaluate_device)")
@@ -116,20 +126,33 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
             keys += [f"ws_feat_{name}", f"ws_feat_std_{name}", *[f"ws_feat_{name}_{i}" for i in range(moe.n_experts)]]
     acc: Dict[str, List[float]] = {k: [] for k in keys}
     seen = 0                                   # test samples in earlier batches
+    conds = []                                 # the batches' device conditions (eval_diagnostics)
     for b, batch in enumerate(test_loader):
         if max_batches is not None and b >= max_batches:
             break
         real_images, _, cond, std, intensity, true_positions = batch
         if on_device:
-            m = moe.evaluate_device(epoch, cond.to(device), real_images, cfg,
+            cond_dev = cond.to(device)
+            m = moe.evaluate_device(epoch, cond_dev, real_images, cfg,
                                     seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=seen,
                                     features=features)
+            if diagnostics:
+                conds.append(cond_dev)
             seen += int(cond.shape[0])
         else:
             m = moe.evaluate(epoch, cond.to(device), real_images, true_positions, std, intensity, cfg, device)
         for k in keys:
             acc[k].append(float(m[k]))
-    return {k: (sum(v) / len(v) if v else 0.0) for k, v in acc.items()}
+    out = {k: (sum(v) / len(v) if v else 0.0) for k, v in acc.items()}
+    if diagnostics and conds:
+        from .diagnostics import save_diagnostics
+        diag = moe.diagnose(torch.cat(conds), seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=0)
+        out["expert_diagnostics"] = diag
+        dir_info = cfg.train.get("dir_info")
+        if dir_info and cfg.train.get("save_experiment_data", False):
+            os.makedirs(str(dir_info), exist_ok=True)
+            save_diagnostics(os.path.join(str(dir_info), f"diagnostics_epoch_{epoch}.npz"), diag)
+    return out
 
 
 def train(cfg, train_loader, test_loader=None, max_steps_per_epoch=None) -> List[Dict]:

@@ -774,6 +774,89 @@ int es_image_sum_peak(const es_view_t* x, int x_f64, const void* xp, double* sum
                       int32_t* peak /* [n, 2] or NULL */, es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Expert diagnostics (the numbers behind the reference's specialisation plots: train/loop.py:234-329,
+ * train/utils.py:470-620, utils/utils_eval.py:44-51; nothing is drawn) -- csrc/diagnostics.hip.
+ * ---------------------------------------------------------------------------------------- */
+/* Both entries read a value matrix x [rows][ld] (x_f64 = 0: fp32, 1: fp64; fp32 is widened exactly, so the
+ * results are those of the fp64 arithmetic below on the widened values), of which the first `cols` columns
+ * count (1 <= cols <= ES_DIAG_MAX_COLS, cols <= ld).  Segments follow es_wasserstein_1d: segment s covers
+ * the rows idx[seg[2s] .. seg[2s+1]) (idx NULL: the rows themselves), in that order; seg [n_seg][2] and idx
+ * [rows] are DEVICE int32 arrays: no host sync, everything runs on `stream`.  The bounds are clamped to
+ * [0, rows], a segment's length to seg_cap (the host's upper bound of it: grid and workspace sizing) and every
+ * row index to [0, rows).  Segments may overlap ("all rows" plus one per expert).  Values must be finite.
+ * 0 <= rows <= 2^20, 1 <= seg_cap, n_seg <= 65535.  Outside the limits stated here and per entry, with a
+ * NULL required pointer, x_f64 not 0 or 1 or too small a workspace: ES_ERR_ARG and nothing is launched.
+ * rows == 0 or n_seg == 0: ES_OK without a launch and NOTHING is written -- the outputs, the counts
+ * included, are then the caller's to initialise.
+ *
+ * The range of column c is lo = min, hi = max of x[0 .. rows)[c] over ALL rows (not the segments'): exact
+ * and order-independent (integer min / max atomics on an order-preserving encoding of the doubles; whether a
+ * zero comes out as -0.0 or +0.0 is unspecified).  linspace(lo, hi, num)[k], k = 0 .. num - 1, is
+ * np.linspace's arithmetic, fp64, no contraction: div = num - 1; delta = hi - lo; step = delta / div;
+ * value = (double)k * step + lo (product rounded, then added) -- or ((double)k / div) * delta + lo when
+ * step == 0 -- and the last value (k = div, num > 1) is hi itself; num == 1 gives lo.  lo == hi gives num
+ * equal values.
+ *
+ * es_segment_histogram.  counts[s][c][b] (int32) = the members of segment s whose column c falls into bin b
+ * of the edges e = edges_out[c][0 .. bins], compared in fp64:
+ *   right = 0   np.histogram(x, bins=e):                   e[b] <= x < e[b+1]; the last bin also holds
+ *               x == e[bins].  With all edges equal every value lands in the last bin.
+ *   right = 1   pd.cut(x, bins=e, include_lowest=True):    e[b] < x <= e[b+1]; bin 0 also holds x == e[0].
+ *               With all edges equal every value lands in bin 0.
+ * The bin is found by a binary search over the edges themselves, so it is the definition exactly (no
+ * multiply-by-reciprocal estimate).  outside[s][c] counts the members below e[0] or above e[bins]; they are in
+ * no bin (possible with caller-given edges only).  edges: a DEVICE array [cols][bins + 1], non-decreasing
+ * per column, copied to edges_out; or NULL: edges_out[c] = linspace(lo_c, hi_c, bins + 1) of the column's
+ * range.  edges_out is always written.  counts and outside are zeroed on the stream, then filled by
+ * integer (vector) atomics on LDS and, to merge the workgroups of a segment, on global memory: order does not
+ * matter, a rerun is bit-equal.
+ * Limits: 1 <= bins and cols * (2 * bins + 1) <= ES_DIAG_HIST_MAX_CELLS (one workgroup's LDS holds the edges
+ * and one histogram per column, at three workgroups per CU).  work: es_segment_histogram_workspace(cols, bins)
+ * bytes (0: outside the limits), needed only when edges is NULL. */
+#define ES_DIAG_MAX_COLS 64
+#define ES_DIAG_HIST_MAX_CELLS 5120
+size_t es_segment_histogram_workspace(int cols, int bins);
+int es_segment_histogram(const void* x, int x_f64, int64_t ld, int rows, int cols, const int32_t* idx,
+                         const int32_t* seg, int n_seg, int seg_cap, int bins, int right,
+                         const double* edges /* [cols, bins + 1] or NULL */,
+                         double* edges_out /* [cols, bins + 1] */, int32_t* counts /* [n_seg, cols, bins] */,
+                         int32_t* outside /* [n_seg, cols] */, void* work, size_t work_bytes,
+                         es_stream_t stream);
+/* es_segment_kde.  1-D Gaussian kernel density estimate, scipy.stats.gaussian_kde(d, bw_method='scott'),
+ * of the n members d_i of (segment s, column c) on the grid g = grid_out[c][0 .. points): the caller's
+ * `grid` (DEVICE [cols][points], copied to grid_out) or, with grid NULL, linspace(lo_c, hi_c, points) of the
+ * column's range, where lo == hi becomes lo - 1e-6, hi + 1e-6 first (train/utils.py:571-607).  fp64
+ * throughout, no contraction, no float atomics.
+ *   S = sum d_i, m = S / (double)n, Q = sum (d_i - m)^2 (product rounded, then added): es_group_diversity's
+ *   fixed order, a function of n only -- n <= ES_PREP_SPLIT_MIN one sequential chain in member order from
+ *   +0.0; above, ES_PREP_CHUNKS chunks [k L, min(n, (k+1) L)), L = ceil(n / ES_PREP_CHUNKS), each summed
+ *   sequentially from +0.0, the chunk sums added in chunk order from +0.0.
+ *   valid[s][c] = 0 when n < max(min_samples, 2) (the reference: 5), sqrt(Q / n) < std_eps (np.std,
+ *   ddof = 0; the reference: 1e-12) or Q == 0 (no bandwidth): bw = 0, sd = 0 and the density row is NaN.  Otherwise valid = 1,
+ *   sd = sqrt(Q / (n - 1)) (np.cov, ddof = 1), bw[s][c] = sd * pow((double)n, -0.2) (Scott; the device
+ *   library's pow, within 16 ulp by the OpenCL bound it conforms to, plus one rounding for the product) and
+ *   density[s][c][j] = T_j / (((double)n * bw) * sqrt(2 pi)),  T_j = sum_i exp(-0.5 * (z * z)),
+ *   z = (g_j - d_i) * r, r = 1.0 / bw computed once (sqrt(2 pi) = 2.5066282746310002).
+ *   T_j in a fixed order that is a function of n only: the members are cut into chunks of
+ *   ES_DIAG_KDE_CHUNK in member order; each chunk is summed sequentially from +0.0 and the chunk sums are
+ *   added in chunk order from +0.0.
+ * A segment's result depends on its members, their order and the grid alone: not on rows, the other
+ * segments, ld, idx against contiguous rows or the number of workgroups; a rerun is bit-equal.
+ * sd (optional, [n_seg][cols]) receives sd.  Limits: 1 <= points <= ES_DIAG_KDE_MAX_POINTS, min_samples >= 0.
+ * work: es_segment_kde_workspace(n_seg, cols, points, seg_cap) bytes (0: outside the limits): the range and
+ * the chunk sums [n_seg][cols][ceil(seg_cap / ES_DIAG_KDE_CHUNK)][points] fp64. */
+#define ES_DIAG_KDE_CHUNK 256
+#define ES_DIAG_KDE_MAX_POINTS 1024
+#define ES_DIAG_RANGE_BYTES 1024   /* the head of both workspaces: min / max keys [2][ES_DIAG_MAX_COLS] */
+size_t es_segment_kde_workspace(int n_seg, int cols, int points, int seg_cap);
+int es_segment_kde(const void* x, int x_f64, int64_t ld, int rows, int cols, const int32_t* idx,
+                   const int32_t* seg, int n_seg, int seg_cap, int points,
+                   const double* grid /* [cols, points] or NULL */, int min_samples, double std_eps,
+                   double* grid_out /* [cols, points] */, double* density /* [n_seg, cols, points] */,
+                   double* bw /* [n_seg, cols] */, int32_t* valid /* [n_seg, cols] */,
+                   double* sd /* [n_seg, cols] or NULL */, void* work, size_t work_bytes, es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
  * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
  * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
