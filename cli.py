@@ -18,7 +18,8 @@ expertsim/utils/data_preparation.py) for the detector named by dataset.zdc_type:
 Expert diagnostics (MoEWrapper.diagnose: per-expert histograms and kernel density estimates of the photon
 sums and the conditioning variables, as arrays) from a saved checkpoint:
     python cli.py -o model.n_experts=3 --diagnose --checkpoint DIR [--checkpoint-epoch E] \
-        --conditions FILE.npy|.pkl --out FILE.npz
+        --conditions FILE.npy|.pkl --out FILE.npz [--embedding [--embedding-iters K]]
+--embedding adds the PCA and exact t-SNE embedding of the conditions by expert (expertsim/train/embedding.py).
 """
 import argparse
 import logging
@@ -52,6 +53,9 @@ def parse_args(args=None):
     x = p.add_argument_group("expert diagnostics (instead of training)")
     x.add_argument("--diagnose", action="store_true",
                    help="per-expert histograms and KDEs for --conditions FILE from --checkpoint DIR, written to --out")
+    x.add_argument("--embedding", action="store_true",
+                   help="with --diagnose: also the PCA / exact t-SNE embedding of the conditions by expert")
+    x.add_argument("--embedding-iters", type=int, default=1000, help="t-SNE iterations of --embedding")
     d = p.add_argument_group("dataset preparation (instead of training)")
     d.add_argument("--prepare", action="store_true",
                    help="compute std, group_number, photon sums and peak positions; write the pickle data source")
@@ -136,7 +140,8 @@ def diagnose(args):
         names = names or [c for c in COND_COLUMNS if c in cond.columns]
         cond = cond[names].to_numpy()
     cond = np.asarray(cond, dtype=np.float32)
-    diag = moe.diagnose(torch.from_numpy(cond), seed=args.seed, names=names)
+    diag = moe.diagnose(torch.from_numpy(cond), seed=args.seed, names=names, embedding=args.embedding,
+                        embedding_iters=args.embedding_iters)
     path = save_diagnostics(args.out, diag)
     logger.info("Diagnostics of %d conditions over %d experts (epoch %d checkpoint) -> %s", cond.shape[0],
                 moe.n_experts, epoch, path)

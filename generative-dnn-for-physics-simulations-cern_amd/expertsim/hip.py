@@ -213,6 +213,13 @@ _SIGS = {
     "es_segment_kde_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "es_segment_kde": (C.c_int, [P, C.c_int, I64, C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, C.c_int,
                                  C.c_double, P, P, P, P, P, P, C.c_size_t, P]),
+    "es_pca_project_workspace": (C.c_size_t, [C.c_int]),
+    "es_pca_project": (C.c_int, [P, C.c_int, I64, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, C.c_size_t, P]),
+    "es_tsne_affinities": (C.c_int, [P, I64, C.c_int, C.c_int, C.c_double, P, P, P, P, P]),
+    "es_tsne_workspace": (C.c_size_t, [C.c_int]),
+    "es_tsne_gradient": (C.c_int, [P, I64, C.c_int, C.c_int, P, P, P, P, C.c_double, P, P, P, C.c_size_t, P]),
+    "es_tsne_run": (C.c_int, [P, I64, C.c_int, C.c_int, P, P, P, P, P, P, C.c_int, C.c_int, C.c_double, C.c_int,
+                              C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, P, C.c_int, P, C.c_size_t, P]),
 }
 
 # es_group_diversity's split of a large group (ES_PREP_SPLIT_MIN / ES_PREP_CHUNKS of include/expertsim_hip.h)
@@ -226,6 +233,24 @@ DIAG_HIST_MAX_CELLS = 5120
 DIAG_KDE_CHUNK = 256
 DIAG_KDE_MAX_POINTS = 1024
 DIAG_RANGE_BYTES = 1024
+
+
+# conditioning embeddings (ES_TSNE_* of include/expertsim_hip.h): the fp32 chain of the pair pass, the most j
+# splits, and the row limits of es_pca_project / es_tsne_*
+TSNE_TILE = 32
+TSNE_MAX_SPLITS = 16
+PCA_MAX_ROWS = 1 << 20
+TSNE_MAX_ROWS = 1 << 17
+
+
+def pca_project_workspace(cols: int) -> int:
+    """Bytes of es_pca_project's workspace: cov and the eigenvector matrix (0: outside the limits)."""
+    return int(lib().es_pca_project_workspace(int(cols)))
+
+
+def tsne_workspace(rows: int) -> int:
+    """Bytes of es_tsne_gradient's / es_tsne_run's workspace (0: outside the limits)."""
+    return int(lib().es_tsne_workspace(int(rows)))
 
 
 def segment_histogram_workspace(cols: int, bins: int) -> int:

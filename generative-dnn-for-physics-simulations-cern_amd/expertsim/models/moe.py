@@ -715,7 +715,7 @@ class MoEWrapper(nn.Module):
 
     @torch.no_grad()
     def diagnose(self, cond, *, seed=0, sample_offset=0, routing="sample", fused=True, graph=True, bins=50,
-                 points=100, names=None):
+                 points=100, names=None, embedding=False, embedding_iters=1000, embedding_max=16384):
         """Expert-specialisation diagnostics of the routed simulation of cond [N, cond_dim] (the last
         variable categorical): the dict of train.diagnostics.expert_diagnostics as host numpy arrays --
         per expert the sample count, the histogram of the generated images' photon sums, the histogram and
@@ -723,7 +723,9 @@ class MoEWrapper(nn.Module):
 
         simulate(cond, domain="photons") with the same seed semantics gives the images and the expert
         vector (that of evaluate_device for the same (seed, sample_offset)); es_image_sum_peak gives the
-        photon sums; es_segment_histogram / es_segment_kde the rest.  Like simulate, reads training state
+        photon sums; es_segment_histogram / es_segment_kde the rest.  embedding=True adds the keys of
+        train.embedding.cond_embedding (PCA and exact t-SNE of at most embedding_max conditions, coloured
+        by the same expert vector; embedding_iters t-SNE iterations).  Like simulate, reads training state
         and changes none; HIP device only."""
         from ..train.diagnostics import expert_diagnostics
         from ..utils.data_preparation import photon_sums_and_peaks
@@ -735,8 +737,13 @@ class MoEWrapper(nn.Module):
             sim = self.simulate(cond, seed=seed, sample_offset=sample_offset, domain="photons", routing=routing,
                                 fused=fused, graph=graph)
             photon_sum, _ = photon_sums_and_peaks(sim["images"], check=False)
-            return expert_diagnostics(cond, sim["expert"], self.n_experts, photon_sum, names=names, bins=bins,
+            diag = expert_diagnostics(cond, sim["expert"], self.n_experts, photon_sum, names=names, bins=bins,
                                       points=points)
+            if embedding:
+                from ..train.embedding import cond_embedding
+                diag.update(cond_embedding(cond, sim["expert"], self.n_experts, max_rows=int(embedding_max),
+                                           n_iter=int(embedding_iters)))
+            return diag
 
     # ---------------------------------------------------------------------------- simulation
     # Philox stream ids of the simulation draws (DeviceRNG's step streams start at 1 << 24)

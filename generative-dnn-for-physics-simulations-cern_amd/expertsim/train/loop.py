@@ -107,10 +107,17 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     the conditions of the whole test set (the reference concatenates the test set for its specialisation
     plots, loop.py:234-329) with seed = train.rng_seed and sample_offset = 0, under
     metrics["expert_diagnostics"]; with train.save_experiment_data and train.dir_info also written to
-    diagnostics_epoch_<epoch>.npz there.  Off: the returned dict and the launches are unchanged."""
+    diagnostics_epoch_<epoch>.npz there.  Off: the returned dict and the launches are unchanged.
+    train.eval_embedding (with eval_diagnostics only): diagnose(embedding=True, embedding_iters=
+    train.eval_embedding_iters, embedding_max=train.eval_embedding_max) -- the PCA / t-SNE keys of
+    train/embedding.py join the diagnostics and the .npz."""
     on_device = bool(cfg.train.get("eval_on_device", False))
     features = bool(cfg.train.get("eval_features", False))
     diagnostics = bool(cfg.train.get("eval_diagnostics", False))
+    embedding = bool(cfg.train.get("eval_embedding", False))
+    if embedding and not diagnostics:
+        raise ValueError("train.eval_embedding needs train.eval_diagnostics: the embedding is part of the expert "
+                         "diagnostics (MoEWrapper.diagnose(embedding=True))")
     if diagnostics and not on_device:
         raise ValueError("train.eval_diagnostics needs train.eval_on_device: the expert diagnostics exist on the "
                          "device path only (MoEWrapper.diagnose)")
@@ -146,7 +153,9 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     out = {k: (sum(v) / len(v) if v else 0.0) for k, v in acc.items()}
     if diagnostics and conds:
         from .diagnostics import save_diagnostics
-        diag = moe.diagnose(torch.cat(conds), seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=0)
+        extra = dict(embedding=True, embedding_iters=int(cfg.train.get("eval_embedding_iters", 1000)),
+                     embedding_max=int(cfg.train.get("eval_embedding_max", 16384))) if embedding else {}
+        diag = moe.diagnose(torch.cat(conds), seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=0, **extra)
         out["expert_diagnostics"] = diag
         dir_info = cfg.train.get("dir_info")
         if dir_info and cfg.train.get("save_experiment_data", False):

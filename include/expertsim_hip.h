@@ -857,6 +857,123 @@ int es_segment_kde(const void* x, int x_f64, int64_t ld, int rows, int cols, con
                    double* sd /* [n_seg, cols] or NULL */, void* work, size_t work_bytes, es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Conditioning embeddings (the numbers behind the reference's plot_cond_pca_tsne, train/utils.py:422-467:
+ * PCA(n_components=2) and TSNE(n_components=2, perplexity=30) of the conditions; nothing is drawn)
+ * -- csrc/embedding.hip.
+ * ---------------------------------------------------------------------------------------- */
+/* The conventions of the expert diagnostics above: x [rows][ld] with unit column stride, of which the first
+ * `cols` columns count (1 <= cols <= ES_DIAG_MAX_COLS, cols <= ld); every pointer is a DEVICE pointer; no
+ * host sync, everything runs on `stream`.  Values must be finite.  Outside the limits stated here and per
+ * entry, with a NULL required pointer or too small a workspace: ES_ERR_ARG before any launch, and
+ * NOTHING is written.  There are no float atomics anywhere: every sum has an order that is a function of the
+ * sizes only, so a rerun is bit-equal.
+ *
+ * es_pca_project.  x fp32 (x_f64 = 0; widened exactly) or fp64 (x_f64 = 1), 2 <= rows <= 2^20, 1 <= k <= cols.
+ * fp64 throughout, no contraction:
+ *   S_c = sum_r x[r][c], mean[c] = S_c / (double)rows;
+ *   Q_ab = sum_r (x[r][a] - mean[a]) * (x[r][b] - mean[b])  (product rounded, then added), computed for a <= b
+ *   and mirrored; cov[a][b] = Q_ab / ((double)rows - 1.0)   (ddof = 1: sklearn.decomposition.PCA(svd_solver=
+ *   'full')'s explained_variance_).  Both sums run in es_group_diversity's fixed order, a function of rows only:
+ *   rows <= ES_PREP_SPLIT_MIN one sequential chain in row order from +0.0; above, ES_PREP_CHUNKS chunks
+ *   [k L, min(rows, (k+1) L)), L = ceil(rows / ES_PREP_CHUNKS), each summed sequentially from +0.0, the chunk
+ *   sums added in chunk order from +0.0.
+ *   The eigenpairs (lambda, v) of the symmetric cols x cols matrix cov come from cyclic Jacobi rotations in one
+ *   workgroup, in row-cyclic order (p, q), p < q; a pair is skipped when cov_pq == 0 or
+ *   |cov_pq| <= 2^-56 sqrt(|cov_pp| |cov_qq|); the sweeps end with the first sweep that rotates nothing (at most
+ *   30).  Components are sorted by decreasing eigenvalue (equal eigenvalues: the lower Jacobi column first).
+ *   Sign: sklearn's svd_flip(u_based_decision=False) -- the entry of largest magnitude of each component is
+ *   positive, the first index wins a tie.
+ *   components[m][c] (m < k), explained_variance[m] = lambda_m, explained_variance_ratio[m] = lambda_m / trace,
+ *   trace = sum_c cov[c][c] in column order from +0.0 (0 when the trace is 0); mean[c];
+ *   scores[r][m] = sum_c (x[r][c] - mean[c]) * components[m][c], columns in order from +0.0, the product rounded,
+ *   then added.  A constant column is legal: its row and column of cov are exactly zero, no rotation touches
+ *   them and its loading is zero in every component with a positive eigenvalue.
+ * work: es_pca_project_workspace(cols) bytes (0: outside the limits): cov and the eigenvector matrix. */
+size_t es_pca_project_workspace(int cols);
+int es_pca_project(const void* x, int x_f64, int64_t ld, int rows, int cols, int k, double* scores /* [rows, k] */,
+                   double* components /* [k, cols] */, double* explained_variance /* [k] */,
+                   double* explained_variance_ratio /* [k] */, double* mean /* [cols] */, void* work,
+                   size_t work_bytes, es_stream_t stream);
+/* es_tsne_affinities.  The per-row scalars of t-SNE's input similarities
+ * (sklearn.manifold._utils._binary_search_perplexity).  x fp32, 2 <= rows <= 2^17, 0 < perplexity < rows
+ * (sklearn's rule).
+ *   d_ij is DEFINED in fp32: acc = +0.0f; for c = 0 .. cols-1 in order: t = x[i][c] - x[j][c]; q = t * t;
+ *   acc = acc + q (the product rounded, then added; no contraction).  So d_ij == d_ji bitwise, duplicate rows
+ *   give exactly 0, and numpy float32 arithmetic reproduces it bit for bit.
+ *   dmin_i = min_{j != i} d_ij (fp32, exact).  In fp64, with dd_ij = (double)d_ij - (double)dmin_i (exact):
+ *   S_i(beta) = sum_{j != i} exp(-beta * dd_ij),   W_i(beta) = sum_{j != i} dd_ij * exp(-beta * dd_ij),
+ *   H_i = log S_i + beta * (W_i / S_i).  The shifted form is the same distribution as sklearn's but cannot
+ *   underflow to an empty row (S_i >= 1).  Order of both sums: thread t of 256 adds j = t, t + 256, .. in that
+ *   order from +0.0; the 64 lane sums of a wave are combined by the butterfly a[l] <- a[l] + a[l ^ o],
+ *   o = 32, 16, 8, 4, 2, 1; the four wave sums are added in wave order from +0.0.  exp and log are the device
+ *   library's fp64 functions.
+ *   Search: beta = 1, lower bound -inf, upper bound +inf; at most 100 evaluations; an evaluation with
+ *   |H - log(perplexity)| <= 1e-5 ends the search; otherwise H too large: lower = beta, beta = beta * 2 while
+ *   the upper bound is +inf, else (beta + upper) / 2; H too small: upper = beta, beta = beta / 2 while the
+ *   lower bound is -inf, else (beta + lower) / 2.
+ *   beta[i] = the beta of the LAST evaluation, log_s[i] = log S_i at that beta, dmin[i], steps[i] = the number
+ *   of evaluations (1 .. 100).  They define the conditional p_{j|i} = exp(-beta_i dd_ij - log_s_i) (j != i) and
+ *   the joint p_ij = (p_{j|i} + p_{i|j}) / (2 rows).
+ *   A row whose nearest distance is shared by m >= perplexity points cannot reach the target (H -> log m): it
+ *   ends with steps = 100 and a large finite beta (2^99 when no upper bound was ever found); that is the
+ *   defined result, not an error. */
+int es_tsne_affinities(const float* x, int64_t ld, int rows, int cols, double perplexity, double* beta /* [rows] */,
+                       double* log_s /* [rows] */, float* dmin /* [rows] */, int32_t* steps /* [rows] */,
+                       es_stream_t stream);
+/* es_tsne_gradient / es_tsne_run.  Exact (all-pairs) t-SNE on the joint p_ij above, matrix-free: p_ij is
+ * recomputed per pair, never stored.  y [rows][2] fp32 (dense).  With w_ij = 1 / (1 + |y_i - y_j|^2):
+ *   Z = sum_{i != j} w_ij,   q_ij = max(w_ij / Z, DBL_EPSILON),
+ *   g_i = 4 sum_j (a p_ij - q_ij) w_ij (y_i - y_j),
+ *   KL = sum_{i != j} p_ij log(max(p_ij, DBL_EPSILON) / q_ij)     (no exaggeration in the KL).
+ * The device evaluates the split form A_i = sum_j p_ij w_ij (y_i - y_j), R_i = sum_j w_ij^2 (y_i - y_j),
+ * Zr_i = sum_j w_ij, K_i = sum_j p_ij (log max(p_ij, DBL_EPSILON) - log w_ij), P_i = sum_j p_ij, then
+ * Z = sum_i Zr_i, g_i = 4 (a A_i - R_i / Z), KL = sum_i K_i + log(Z) sum_i P_i: identical except where the
+ * clamp of q binds (w_ij / Z < DBL_EPSILON, an embedding 10^7 wide), where it differs by at most
+ * 4 sum_j max(0, DBL_EPSILON - w_ij / Z) w_ij |y_i - y_j| per row.
+ * Pair math is fp32 (v_exp_f32 and v_rcp_f32, 1 ulp each): b_i = fl32(beta_i log2 e) and
+ * l_i = fl32(log_s_i log2 e + log2(2 rows)) (the fp64 expressions rounded once);
+ * p_ij = exp2(-b_i (d_ij - dmin_i) - l_i) + exp2(-b_j (d_ij - dmin_j) - l_j) with d_ij as above (direct
+ * differences: d_ij == 0 for duplicates); exp2 flushes results below 2^-126 to zero;
+ * w_ij = rcp(1 + dy0^2 + dy1^2).  The pair j == i contributes exactly zero.
+ * Order of the five (seven) row sums: fp32 along a tile of ES_TSNE_TILE consecutive columns j in j order from
+ * +0.0f (a fused multiply-add per term where the target has one); the tile sums are added in fp64 in tile order
+ * from +0.0; the columns are cut into n_s = min(ES_TSNE_MAX_SPLITS, ceil(rows / 256)) splits
+ * [s L, min(rows, (s+1) L)), L = 4 ES_TSNE_TILE * ceil(ceil(rows / n_s) / (4 ES_TSNE_TILE)) (a split may be
+ * empty; its tiles start at its first column),
+ * and a row's split sums are added in split order from +0.0.  Sums over rows (Z, K, P, |g|^2): thread t of
+ * 1024 adds the rows (elements) t, t + 1024, .. in that order from +0.0, then the wave butterfly of
+ * es_tsne_affinities, then the 16 wave sums in wave order from +0.0.
+ *
+ * es_tsne_gradient writes g [rows][2] fp64 at the given y and a = exaggeration, and z_kl[0] = Z, z_kl[1] = KL.
+ * es_tsne_run runs the iterations t = iter0 .. iter0 + n_iter - 1 on y in place with the same device code and
+ * sklearn's _gradient_descent update, element-wise, fp64, no contraction.  State: upd, gains [rows][2] fp64
+ * (before iteration 0 the caller zeroes upd and sets gains to 1).  With a = exaggeration and mu = momentum0
+ * while t < exaggeration_iters, else a = 1 and mu = momentum1:
+ *   inc = upd * g < 0;  gains = inc ? gains + 0.2 : gains * 0.8;  gains = max(gains, min_gain);
+ *   upd = mu * upd - learning_rate * (g * gains);   y = (float)((double)y + upd).
+ * sklearn's defaults: exaggeration 12, exaggeration_iters 250, momentum0 0.5, momentum1 0.8, min_gain 0.01,
+ * learning_rate 'auto' = max(rows / exaggeration / 4, 50), check_every 50.  iter0 is the global index of the
+ * first iteration, so a run can be split into calls: one call of n equals two calls that split it, bit for bit.
+ * log: when (t + 1) % check_every == 0, and after the last iteration of the call, row t / check_every of
+ * log [log_rows][2] fp64 receives (KL, |g|_2) of iteration t (at the y before its update; |g|_2 with that
+ * iteration's a); log_rows > (iter0 + n_iter - 1) / check_every.  n_iter == 0: ES_OK without a launch.
+ * sklearn's two early-stop rules (n_iter_without_progress, min_grad_norm) are NOT rebuilt: the run has no host
+ * round trip, and sklearn itself ran 999 of 1000 iterations on the golden's data.
+ * work: es_tsne_workspace(rows) bytes (0: outside the limits): the split sums [n_s][rows][8] fp64, g, three
+ * scalars, b and l. */
+#define ES_TSNE_TILE 32
+#define ES_TSNE_MAX_SPLITS 16
+size_t es_tsne_workspace(int rows);
+int es_tsne_gradient(const float* x, int64_t ld, int rows, int cols, const double* beta, const double* log_s,
+                     const float* dmin, const float* y, double exaggeration, double* g /* [rows, 2] */,
+                     double* z_kl /* [2] */, void* work, size_t work_bytes, es_stream_t stream);
+int es_tsne_run(const float* x, int64_t ld, int rows, int cols, const double* beta, const double* log_s,
+                const float* dmin, float* y, double* upd, double* gains, int n_iter, int iter0,
+                double exaggeration, int exaggeration_iters, double momentum0, double momentum1,
+                double learning_rate, double min_gain, int check_every, double* log /* [log_rows, 2] */,
+                int log_rows, void* work, size_t work_bytes, es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
  * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
  * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
