@@ -13,13 +13,18 @@ Simulation (conditions in, calorimeter images out; MoEWrapper.simulate) from a s
 Dataset preparation (raw responses + particle conditions in, the three pickles of dataset.source=pickle out;
 expertsim/utils/data_preparation.py) for the detector named by dataset.zdc_type:
     python cli.py -o dataset.zdc_type=neutron --prepare --images FILE.npy|.pkl --conditions FILE.pkl|.npy \
-        [--cond-columns NAME ...] [--raw] [--min-photon-sum X] [--max-photon-sum X] --out-dir DIR
+        [--cond-columns NAME ...] [--raw] [--min-photon-sum X] [--max-photon-sum X] --out-dir DIR \
+        [--clusters K [--cluster-seed S] [--cluster-restarts R]]
+--clusters K (proton sets) writes the expert_number column from a k-means of the images into K clusters
+(expertsim/utils/clustering.py).
 
 Expert diagnostics (MoEWrapper.diagnose: per-expert histograms and kernel density estimates of the photon
 sums and the conditioning variables, as arrays) from a saved checkpoint:
     python cli.py -o model.n_experts=3 --diagnose --checkpoint DIR [--checkpoint-epoch E] \
-        --conditions FILE.npy|.pkl --out FILE.npz [--embedding [--embedding-iters K]]
+        --conditions FILE.npy|.pkl --out FILE.npz [--embedding [--embedding-iters K]] [--expert-number FILE.npy]
 --embedding adds the PCA and exact t-SNE embedding of the conditions by expert (expertsim/train/embedding.py).
+--expert-number adds the router's agreement with that class vector (confusion matrix, accuracy, macro
+precision / recall / F1, matched accuracy, adjusted Rand index) as router_agreement.* arrays.
 """
 import argparse
 import logging
@@ -56,6 +61,8 @@ def parse_args(args=None):
     x.add_argument("--embedding", action="store_true",
                    help="with --diagnose: also the PCA / exact t-SNE embedding of the conditions by expert")
     x.add_argument("--embedding-iters", type=int, default=1000, help="t-SNE iterations of --embedding")
+    x.add_argument("--expert-number", type=str, default=None,
+                   help="with --diagnose: .npy class vector [N] (expert_number) to compare the routing against")
     d = p.add_argument_group("dataset preparation (instead of training)")
     d.add_argument("--prepare", action="store_true",
                    help="compute std, group_number, photon sums and peak positions; write the pickle data source")
@@ -68,6 +75,10 @@ def parse_args(args=None):
     d.add_argument("--min-photon-sum", type=float, default=None, help="keep samples with photon sum >= this")
     d.add_argument("--max-photon-sum", type=float, default=None, help="keep samples with photon sum <= this")
     d.add_argument("--out-dir", type=str, default=None, help="directory for the three pickles")
+    d.add_argument("--clusters", type=int, default=None,
+                   help="proton sets: write expert_number from a k-means of the images into this many clusters")
+    d.add_argument("--cluster-seed", type=int, default=0, help="seed of the k-means++ draws of --clusters")
+    d.add_argument("--cluster-restarts", type=int, default=10, help="k-means restarts of --clusters")
     return p.parse_args(args)
 
 
@@ -140,8 +151,9 @@ def diagnose(args):
         names = names or [c for c in COND_COLUMNS if c in cond.columns]
         cond = cond[names].to_numpy()
     cond = np.asarray(cond, dtype=np.float32)
+    expert_number = np.load(args.expert_number) if args.expert_number else None
     diag = moe.diagnose(torch.from_numpy(cond), seed=args.seed, names=names, embedding=args.embedding,
-                        embedding_iters=args.embedding_iters)
+                        embedding_iters=args.embedding_iters, expert_number=expert_number)
     path = save_diagnostics(args.out, diag)
     logger.info("Diagnostics of %d conditions over %d experts (epoch %d checkpoint) -> %s", cond.shape[0],
                 moe.n_experts, epoch, path)
@@ -174,7 +186,9 @@ def prepare(args):
     cond = _load_array_or_pickle(args.conditions)
     if not isinstance(cond, pd.DataFrame):
         cond = pd.DataFrame(np.asarray(cond), columns=args.cond_columns or DP.COND_COLUMNS)
-    images, cond_out, positions = DP.prepare_dataset(images, cond, zdc, args.min_photon_sum, args.max_photon_sum)
+    images, cond_out, positions = DP.prepare_dataset(images, cond, zdc, args.min_photon_sum, args.max_photon_sum,
+                                                     n_clusters=args.clusters, cluster_seed=args.cluster_seed,
+                                                     cluster_restarts=args.cluster_restarts)
     paths = DP.write_dataset(args.out_dir, zdc, images, cond_out, positions, cfg=cfg)
     group_col = "group_number_proton" if zdc == "proton" else "group_number"
     sizes = np.bincount(cond_out[group_col].to_numpy()) if len(cond_out) else np.zeros(0, dtype=np.int64)

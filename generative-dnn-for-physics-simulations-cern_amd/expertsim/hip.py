@@ -220,6 +220,14 @@ _SIGS = {
     "es_tsne_gradient": (C.c_int, [P, I64, C.c_int, C.c_int, P, P, P, P, C.c_double, P, P, P, C.c_size_t, P]),
     "es_tsne_run": (C.c_int, [P, I64, C.c_int, C.c_int, P, P, P, P, P, P, C.c_int, C.c_int, C.c_double, C.c_int,
                               C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, P, C.c_int, P, C.c_size_t, P]),
+    "es_kmeans_trials": (C.c_int, [C.c_int]),
+    "es_kmeans_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "es_kmeans_plusplus_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "es_kmeans_assign": (C.c_int, [P, C.c_int, I64, C.c_int, C.c_int, P, C.c_int, P, P, P, P, P, P, C.c_size_t, P]),
+    "es_kmeans_update": (C.c_int, [P, C.c_int, I64, C.c_int, C.c_int, P, P, P, C.c_int, P, P, P, C.c_size_t, P]),
+    "es_kmeans_plusplus": (C.c_int, [P, C.c_int, I64, C.c_int, C.c_int, C.c_int, P, C.c_int, P, P, P, C.c_size_t,
+                                     P]),
+    "es_confusion_matrix": (C.c_int, [P, P, I64, C.c_int, C.c_int, P, P, P]),
 }
 
 # es_group_diversity's split of a large group (ES_PREP_SPLIT_MIN / ES_PREP_CHUNKS of include/expertsim_hip.h)
@@ -241,6 +249,23 @@ TSNE_TILE = 32
 TSNE_MAX_SPLITS = 16
 PCA_MAX_ROWS = 1 << 20
 TSNE_MAX_ROWS = 1 << 17
+
+
+# clustering (ES_KMEANS_* / ES_CONFUSION_MAX_CELLS of include/expertsim_hip.h)
+KMEANS_MAX_ROWS = 1 << 24
+KMEANS_MAX_COLS = 4096
+KMEANS_MAX_K = 64
+CONFUSION_MAX_CELLS = 4096
+
+
+def kmeans_workspace(rows: int, cols: int, k: int) -> int:
+    """Bytes of es_kmeans_assign's / es_kmeans_update's workspace (0: outside the limits)."""
+    return int(lib().es_kmeans_workspace(int(rows), int(cols), int(k)))
+
+
+def kmeans_plusplus_workspace(rows: int, cols: int, k: int) -> int:
+    """Bytes of es_kmeans_plusplus's workspace (0: outside the limits)."""
+    return int(lib().es_kmeans_plusplus_workspace(int(rows), int(cols), int(k)))
 
 
 def pca_project_workspace(cols: int) -> int:

@@ -715,7 +715,8 @@ class MoEWrapper(nn.Module):
 
     @torch.no_grad()
     def diagnose(self, cond, *, seed=0, sample_offset=0, routing="sample", fused=True, graph=True, bins=50,
-                 points=100, names=None, embedding=False, embedding_iters=1000, embedding_max=16384):
+                 points=100, names=None, embedding=False, embedding_iters=1000, embedding_max=16384,
+                 expert_number=None):
         """Expert-specialisation diagnostics of the routed simulation of cond [N, cond_dim] (the last
         variable categorical): the dict of train.diagnostics.expert_diagnostics as host numpy arrays --
         per expert the sample count, the histogram of the generated images' photon sums, the histogram and
@@ -725,8 +726,9 @@ class MoEWrapper(nn.Module):
         vector (that of evaluate_device for the same (seed, sample_offset)); es_image_sum_peak gives the
         photon sums; es_segment_histogram / es_segment_kde the rest.  embedding=True adds the keys of
         train.embedding.cond_embedding (PCA and exact t-SNE of at most embedding_max conditions, coloured
-        by the same expert vector; embedding_iters t-SNE iterations).  Like simulate, reads training state
-        and changes none; HIP device only."""
+        by the same expert vector; embedding_iters t-SNE iterations).  expert_number [N] (the proton sets'
+        class column) adds "router_agreement": train.diagnostics.router_agreement of the same expert vector
+        against it.  Like simulate, reads training state and changes none; HIP device only."""
         from ..train.diagnostics import expert_diagnostics
         from ..utils.data_preparation import photon_sums_and_peaks
         dev = next(self.parameters()).device
@@ -743,6 +745,16 @@ class MoEWrapper(nn.Module):
                 from ..train.embedding import cond_embedding
                 diag.update(cond_embedding(cond, sim["expert"], self.n_experts, max_rows=int(embedding_max),
                                            n_iter=int(embedding_iters)))
+            if expert_number is not None:
+                from ..train.diagnostics import router_agreement
+                target = torch.as_tensor(np.asarray(expert_number) if not isinstance(expert_number, torch.Tensor)
+                                         else expert_number)
+                if target.is_floating_point():
+                    target = target.round().long()
+                if tuple(target.shape) != (cond.shape[0],):
+                    raise ValueError(f"expert_number must be [{cond.shape[0]}], got {tuple(target.shape)}")
+                n_true = max(self.n_experts, int(target.max()) + 1) if target.numel() else self.n_experts
+                diag["router_agreement"] = router_agreement(sim["expert"], target.to(dev), self.n_experts, n_true)
             return diag
 
     # ---------------------------------------------------------------------------- simulation

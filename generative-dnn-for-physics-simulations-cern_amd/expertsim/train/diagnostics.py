@@ -221,10 +221,101 @@ def expert_diagnostics(cond, expert, n_experts, photon_sum, names=None, bins=50,
     return out
 
 
+def confusion_matrix(pred, target, n_pred, n_true):
+    """es_confusion_matrix: (counts int64 [n_true, n_pred], invalid int64 [1]) device tensors; counts[t, p] = the
+    pairs with target == t and pred == p, invalid = the pairs with an index outside either range (in no cell).
+    pred / target: integer tensors [n], host or device.  No host synchronisation; runs on the current stream."""
+    if not torch.cuda.is_available():
+        raise hip.HipError("the confusion matrix needs a HIP device (no CPU fallback)")
+    p = pred if isinstance(pred, torch.Tensor) else torch.as_tensor(np.asarray(pred))
+    t = target if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target))
+    if p.dim() != 1 or t.shape != p.shape:
+        raise ValueError(f"pred {tuple(p.shape)} and target {tuple(t.shape)} must be equal-length vectors")
+    if p.is_floating_point() or t.is_floating_point():
+        raise ValueError("pred and target must hold integers")
+    n_pred, n_true = int(n_pred), int(n_true)
+    if n_pred < 1 or n_true < 1 or n_pred * n_true > hip.CONFUSION_MAX_CELLS:
+        raise ValueError(f"confusion matrix {n_true} x {n_pred} outside 1 <= cells <= {hip.CONFUSION_MAX_CELLS}")
+    dev = p.device if p.is_cuda else (t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    lo, hi = torch.iinfo(torch.int32).min, torch.iinfo(torch.int32).max
+    p = p.to(dev).clamp(lo, hi).to(torch.int32).contiguous()    # a wider index stays outside the ranges
+    t = t.to(dev).clamp(lo, hi).to(torch.int32).contiguous()
+    counts = torch.zeros(n_true, n_pred, dtype=torch.int64, device=dev)
+    invalid = torch.zeros(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        hip.call("es_confusion_matrix", hip.ptr(p), hip.ptr(t), int(p.numel()), n_true, n_pred, hip.ptr(counts),
+                 hip.ptr(invalid), hip.stream_ptr())
+    return counts, invalid
+
+
+def agreement_metrics(counts) -> dict:
+    """Host numbers from a confusion matrix counts[target, pred] (int, any shape; classes are 0 .. max(shape)-1):
+
+      accuracy          trace / total (sklearn.metrics.accuracy_score)
+      precision, recall, f1   macro averages over the classes that occur in pred or target, an undefined term
+                        (0 / 0) counting as 0: precision_recall_fscore_support(average="macro", zero_division=0)
+      adjusted_rand     sklearn.metrics.adjusted_rand_score, from the pair counts of the matrix
+      matched_accuracy  the accuracy under the best one-to-one relabelling of the predictions
+                        (scipy.optimize.linear_sum_assignment on the matrix)
+
+    The last two do not depend on how the two sides number their classes.  An empty matrix gives zeros (and
+    adjusted_rand 1, sklearn's value for trivial labelings)."""
+    from scipy.optimize import linear_sum_assignment
+    cm = np.asarray(counts, dtype=np.int64)
+    k = max(cm.shape)
+    sq = np.zeros((k, k), dtype=np.int64)
+    sq[:cm.shape[0], :cm.shape[1]] = cm
+    total = int(sq.sum())
+    tp = np.diag(sq).astype(np.float64)
+    n_t, n_p = sq.sum(axis=1).astype(np.float64), sq.sum(axis=0).astype(np.float64)
+    present = (n_t + n_p) > 0
+
+    def ratio(a, b):
+        return np.divide(a, b, out=np.zeros_like(a), where=b > 0)
+
+    prec, rec = ratio(tp, n_p), ratio(tp, n_t)
+    f1 = ratio(2.0 * tp, n_t + n_p)
+    macro = lambda v: float(v[present].mean()) if present.any() else 0.0
+    # adjusted Rand index from the pair confusion matrix, in Python integers (no overflow)
+    sum_sq = int((sq.astype(object) ** 2).sum())
+    c11 = sum_sq - total
+    c01 = int((sq.astype(object) * sq.sum(axis=0).astype(object)[None, :]).sum()) - sum_sq
+    c10 = int((sq.astype(object) * sq.sum(axis=1).astype(object)[:, None]).sum()) - sum_sq
+    c00 = total * total - c01 - c10 - sum_sq
+    tn, fp, fn, tp2 = c00, c01, c10, c11
+    if fn == 0 and fp == 0:
+        ari = 1.0
+    else:
+        ari = 2.0 * (tp2 * tn - fn * fp) / ((tp2 + fn) * (fn + tn) + (tp2 + fp) * (fp + tn))
+    rows, cols = linear_sum_assignment(-sq)
+    return {"accuracy": float(np.diag(sq).sum()) / total if total else 0.0, "precision": macro(prec),
+            "recall": macro(rec), "f1": macro(f1), "adjusted_rand": float(ari),
+            "matched_accuracy": float(sq[rows, cols].sum()) / total if total else 0.0}
+
+
+def router_agreement(pred, target, n_pred, n_true) -> dict:
+    """How well the router's arg-max `pred` [n] agrees with a class vector `target` [n] (the proton sets'
+    expert_number): {"confusion" int64 [n_true, n_pred] (host), "invalid" (pairs outside either range, counted
+    in no cell), and the numbers of `agreement_metrics`}.  The matrix comes from es_confusion_matrix; one copy
+    brings it to the host.  Cluster numbers and expert numbers are unrelated namings, so matched_accuracy and
+    adjusted_rand are the ones to read across them."""
+    counts, invalid = confusion_matrix(pred, target, n_pred, n_true)
+    flat = torch.cat([counts.reshape(-1), invalid]).cpu().numpy()          # the one copy
+    cm = flat[:-1].reshape(int(n_true), int(n_pred)).copy()
+    return {"confusion": cm, "invalid": int(flat[-1]), **agreement_metrics(cm)}
+
+
 def save_diagnostics(path, diag) -> str:
-    """Write the dict of expert_diagnostics as an .npz; returns the path written."""
+    """Write the dict of expert_diagnostics as an .npz; returns the path written.  A nested dict
+    ("router_agreement") is written as "<key>.<entry>" arrays."""
     path = str(path)
     if not path.endswith(".npz"):
         path += ".npz"
-    np.savez(path, **{k: np.asarray(v) for k, v in diag.items()})
+    flat = {}
+    for k, v in diag.items():
+        if isinstance(v, dict):
+            flat.update({f"{k}.{sk}": np.asarray(sv) for sk, sv in v.items()})
+        else:
+            flat[k] = np.asarray(v)
+    np.savez(path, **flat)
     return path

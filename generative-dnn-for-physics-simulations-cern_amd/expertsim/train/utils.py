@@ -8,6 +8,7 @@ Same names, arguments and return conventions as the reference:
   calculate_joint_ws_across_experts(...)            train/utils.py:117-176
   get_predictions_from_generator_results(...)       train/utils.py:179-205
   get_predictions_from_experts_results(...)         train/utils.py:208-266   (routed, device-side dispatch)
+  evaluate_router(router, y, expert_number, ...)    train/utils.py:299-310   (es_confusion_matrix metrics)
 
 MI355X design: the generated images never leave the device.  Each generator batch is produced in
 HBM (eval mode: BatchNorm running statistics, no dropout), and the fused HIP kernel
@@ -240,6 +241,40 @@ def get_predictions_from_experts_results(num_samples, noise_dim, device, y_test,
             hip.call("es_sim_finish", C.byref(v), h6.ptr, hip.ptr(live), hip.ptr(perm), hip.ptr(offs[e:e + 1]), 1,
                      hip.ptr(dst), None, hip.stream_ptr())
     return out.double().cpu().numpy().reshape(num_samples, *shape_images)
+
+
+@torch.no_grad()
+def evaluate_router(router_network, y_test, expert_number_test, accuracy_metric=None, precision_metric=None,
+                    recall_metric=None, f1_metric=None):
+    """Reference API (train/utils.py:299-310): (accuracy, precision, recall, f1) of the router's arg-max over
+    the conditions y_test against the class column expert_number_test, as host floats.
+
+    The router is put in eval mode and called as ``router_network(y_test)``; a router that returns
+    ``(gates, logits)`` (this project's and the reference's RouterNetwork) is read through its logits, the
+    arg-max free of the Gumbel draw.  A metric callable that is given is called as the reference calls it,
+    ``metric(predicted_labels, expert_number_test).cpu().item()``.  One that is None is computed from
+    es_confusion_matrix (train.diagnostics.agreement_metrics): accuracy, and macro-averaged precision, recall
+    and F1 over the classes that occur, with zero for an undefined term.  HIP device only."""
+    from .diagnostics import agreement_metrics, confusion_matrix
+    router_network.eval()
+    first = next(iter(router_network.parameters()), None) if hasattr(router_network, "parameters") else None
+    y = _cond_on(y_test, first.device) if first is not None else y_test
+    predicted_expert = router_network(y)
+    if isinstance(predicted_expert, (tuple, list)):
+        predicted_expert = predicted_expert[1]
+    _, predicted_labels = torch.max(predicted_expert, 1)
+    target = torch.as_tensor(expert_number_test).to(predicted_labels.device)
+    if target.is_floating_point():
+        target = target.round().long()
+    given = (accuracy_metric, precision_metric, recall_metric, f1_metric)
+    own = None
+    if any(m is None for m in given):
+        n_pred = int(predicted_expert.shape[1])
+        n_cls = max(n_pred, int(target.max()) + 1) if target.numel() else n_pred
+        counts, _ = confusion_matrix(predicted_labels, target, n_cls, n_cls)
+        own = agreement_metrics(counts.cpu().numpy())
+    names = ("accuracy", "precision", "recall", "f1")
+    return tuple(own[k] if m is None else m(predicted_labels, target).cpu().item() for k, m in zip(names, given))
 
 
 # ------------------------------------------------------------------------------ device Wasserstein

@@ -16,9 +16,10 @@ write.  With x the stored, log1p-domain images [N,H,W] and c the [N,9] float64 m
 The one deliberate difference from the notebooks: when every group has a single member every group_sum
 is 0 and pandas gives 0/0 = NaN; `diversity` returns zeros and logs a warning.
 
-The proton sets' ``expert_number`` column comes from a separate offline clustering of the images and is out
-of scope: `prepare_dataset` keeps an ``expert_number`` column the frame already has (or takes one as an
-argument) and otherwise writes zeros, one cluster, with a warning.
+The proton sets' ``expert_number`` column is a clustering of the images: `prepare_dataset(n_clusters=K)` computes
+it on the device (utils/clustering.py: k-means of the filtered images, clusters numbered from the faintest).
+Without n_clusters it keeps an ``expert_number`` column the frame already has (or takes one as an argument) and
+otherwise writes zeros, one cluster, with a warning.
 
 There is no CPU fallback: without a HIP device every device function raises (hip.HipError).
 Only load pickles you produced yourself: unpickling executes code from the file.
@@ -221,7 +222,7 @@ def assemble_frames(cond_frame, zdc_type, std, group, photon_sum, peak, expert_n
         if expert_number is None and "expert_number" in cond_frame.columns:
             expert_number = cond_frame["expert_number"].to_numpy()
         if expert_number is None:
-            logger.warning("no expert_number given: writing zeros (the proton clustering is a separate offline step)")
+            logger.warning("no expert_number given: writing zeros (prepare_dataset(n_clusters=K) clusters the images)")
             expert_number = np.zeros(n, dtype=np.int64)
         out["expert_number"] = np.asarray(expert_number)
     else:
@@ -234,16 +235,27 @@ def assemble_frames(cond_frame, zdc_type, std, group, photon_sum, peak, expert_n
 
 
 def prepare_dataset(images, cond_frame, zdc_type, min_photon_sum=None, max_photon_sum=None, device=None,
-                    expert_number=None):
+                    expert_number=None, n_clusters=None, cluster_seed=0, cluster_restarts=10):
     """images [N,H,W] (log1p domain, fp32 / fp64, host or device) + the particle conditions frame ->
     (images, cond_frame, positions_frame) ready for write_dataset / the ``pickle`` source.
 
     The photon-sum filter is applied first (on the neutron frame's own neutron_photon_sum when it has one,
     else on the computed sums), then std / group_number / photon sum are added and the positions frame is
-    built.  Device copies out: the packed sums and peaks, diversity's two flags and the std column."""
+    built.  Device copies out: the packed sums and peaks, diversity's two flags and the std column.
+
+    n_clusters (proton sets only): ``expert_number`` = clustering.cluster_images of the filtered images into
+    that many clusters (k-means++ with cluster_restarts restarts from cluster_seed).  It excludes a given
+    expert_number -- the argument or a column of the frame -- and a neutron set: ValueError."""
     zdc = _zdc(zdc_type)
     ps_col = _photon_sum_column(zdc)
     cond_frame = cond_frame.reset_index(drop=True)
+    if n_clusters is not None:
+        if zdc != ZDCType.PROTON.value:
+            raise ValueError("n_clusters: only the proton sets have an expert_number column")
+        if expert_number is not None or "expert_number" in cond_frame.columns:
+            raise ValueError("n_clusters together with a given expert_number: choose one")
+        if int(n_clusters) < 1:
+            raise ValueError(f"n_clusters = {n_clusters}")
     if len(cond_frame) != len(images):
         raise ValueError(f"{len(images)} images but {len(cond_frame)} condition rows")
     x = _as_device_images(images, device)
@@ -266,6 +278,10 @@ def prepare_dataset(images, cond_frame, zdc_type, min_photon_sum=None, max_photo
             expert_number = np.asarray(expert_number)[keep]
     group, n_groups = group_numbers(cond_frame[COND_COLUMNS].to_numpy(dtype=np.float64))
     std, _ = diversity(x, group, n_groups)
+    if n_clusters is not None:
+        from .clustering import cluster_images
+        expert_number = cluster_images(x, int(n_clusters), n_init=int(cluster_restarts),
+                                       seed=int(cluster_seed))[0].cpu().numpy()
     cond_out, positions = assemble_frames(cond_frame, zdc, std.cpu().numpy(), group, sums, peak, expert_number)
     host_images = images.cpu().numpy() if isinstance(images, torch.Tensor) else np.asarray(images)
     return host_images, cond_out, positions

@@ -974,6 +974,89 @@ int es_tsne_run(const float* x, int64_t ld, int rows, int cols, const double* be
                 int log_rows, void* work, size_t work_bytes, es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Clustering (the proton sets' expert_number column: scikit-learn's KMeans(algorithm="lloyd"), k-means++) and
+ * the confusion matrix behind the reference's evaluate_router (train/utils.py:299-310) -- csrc/cluster.hip.
+ * ---------------------------------------------------------------------------------------- */
+/* x [rows][ld] with unit column stride (x_f64 = 0: fp32, widened exactly; 1: fp64), of which the first `cols`
+ * columns count.  1 <= rows <= ES_KMEANS_MAX_ROWS, 1 <= cols <= ES_KMEANS_MAX_COLS, cols <= ld,
+ * 1 <= K <= ES_KMEANS_MAX_K, K <= rows.  Centres are fp64 [K][cols], dense.  Every pointer is a DEVICE pointer;
+ * no host sync, everything runs on `stream`.  Values must be finite.  Outside the limits, with a NULL required
+ * pointer, x_f64 not 0 or 1 or too small a workspace: ES_ERR_ARG before any launch, and nothing is written.
+ * All arithmetic on values is fp64 without contraction; there are no float atomics and every sum has an order
+ * that is a function of the sizes only, so a rerun is bit-equal.
+ *
+ * d(r, k), the squared distance of row r to centre k, is the sum of differences
+ *   lane l of 64: a_l = +0.0; for c = l, l + 64, .. < cols in order: t = x[r][c] - centre[k][c]; q = t * t;
+ *   a_l = a_l + q;  then the butterfly a[l] <- a[l] + a[l ^ o], o = 32, 16, 8, 4, 2, 1.
+ * It is NOT the |x|^2 - 2 x.c + |c|^2 expansion scikit-learn uses: the difference form is translation invariant,
+ * so scikit-learn's mean-centring of x (there to tame the expansion's cancellation) is unnecessary here, a row
+ * equal to a centre is at distance exactly 0 and equal centres are at exactly equal distances.
+ * sum_rows(v), a sum over the rows: chunks of 4096 rows; in a chunk thread t of 1024 adds the rows t, t + 1024,
+ * t + 2048, t + 3072 in that order from +0.0, the 64 lane sums of a wave are combined by the butterfly above and
+ * the 16 wave sums are added in wave order from +0.0; the chunk sums are added the same way (thread t adds the
+ * chunks t, t + 1024, ..).
+ *
+ * es_kmeans_assign.  label[r] = the k of smallest d(r, k), the lowest k on a tie; dist[r] = that d;
+ * changed[0] = the rows with label[r] != label_old[r] (label_old NULL, the first iteration: rows; label_old must
+ * not be label); inertia[0] = sum_rows(dist).
+ *
+ * es_kmeans_update.  New centres from the labels (entries outside [0, K) are clamped), scikit-learn's M-step:
+ *   S[k][c] = the sum of x[r][c] over the rows labelled k: the rows are cut into
+ *   n_c = min(256, ceil(rows / 256), max(1, floor(2^24 / (K cols)))) chunks [i L, min(rows, (i+1) L)),
+ *   L = ceil(rows / n_c); inside a chunk the rows are added in row order from +0.0, the chunk sums in chunk order
+ *   from +0.0.  n[k] = the number of rows labelled k.
+ *   Empty clusters (_relocate_empty_clusters_dense): the j-th empty cluster in ascending index takes the row p_j
+ *   that is j-th in the order of descending dist, the lower row first on a tie; for j ascending,
+ *   S[label[p_j]] -= x[p_j], n[label[p_j]] -= 1, S[empty_j] = x[p_j], n[empty_j] = 1; labels are not changed.
+ *   scikit-learn leaves the order among SEVERAL empty clusters to np.argpartition; the rule here is pinned
+ *   against scikit-learn for one empty cluster only.
+ *   centres_new[k][c] = S[k][c] * (1.0 / (double)n[k]) (n[k] == 0: S[k][c] as it stands).
+ *   shift[0] = sum_k sum_c (centres_new - centres_old)^2: per (k, 128-column tile) the butterfly over each of its
+ *   two waves, wave 0 + wave 1; the K * ceil(cols / 128) tile sums, k-major, by lane l of 64 adding l, l + 64, ..
+ *   from +0.0 and the butterfly.  centres_new must not be centres_old.  dist is es_kmeans_assign's, read only when
+ *   a cluster is empty.
+ * work: es_kmeans_workspace(rows, cols, K) bytes for both (0: outside the limits): the reduction chunks, the
+ * update's chunk sums [n_c][K][cols] fp64 and its tile sums.
+ *
+ * es_kmeans_plusplus.  Greedy k-means++ (sklearn.cluster._kmeans._kmeans_plusplus) on the caller's uniform draws
+ * u [K][trials] in [0, 1), trials = es_kmeans_trials(K) = 2 + (int)ln K for scikit-learn's rule (1 .. 8 accepted).
+ *   index[0] = min(floor(u[0][0] * rows), rows - 1); closest[r] = d(r, x[index[0]]).
+ *   Step s = 1 .. K-1: cum = the prefix sums of closest in this order: 1024 segments of Ls = ceil(rows / 1024)
+ *   consecutive rows; local_i = the sequential sum of the segment's rows up to and including i, from +0.0;
+ *   off_t = the segment totals added in segment order from +0.0; cum[i] = off_t + local_i (non-decreasing by
+ *   construction); total = cum[rows - 1].  Candidate j < trials: v = u[s][j] * total,
+ *   cand_j = min(the first i with cum[i] >= v, rows - 1) (np.searchsorted, side='left', clipped).
+ *   pot_j = sum_rows(min(closest[r], d(r, x[cand_j]))); the candidate of lowest pot_j wins, the first on a tie;
+ *   index[s] = cand_j, closest = that minimum.
+ *   centres[s] = x[index[s]] widened.  d() uses the row as the centre: d(r, r) is exactly 0.
+ * work: es_kmeans_plusplus_workspace(rows, cols, K) bytes: closest and eight candidates' distances.
+ *
+ * es_confusion_matrix.  counts[t][p] (int64 [n_true][n_pred]) = the pairs i < n with target[i] == t and
+ * pred[i] == p; invalid[0] = the pairs with an index outside either range, which are in no cell.  Both are zeroed
+ * on the stream and filled by integer adds only (an int32 LDS histogram per workgroup, then 64-bit integer
+ * atomics on global memory), so the result does not depend on any order.  n == 0 is legal (all zeros).
+ * 1 <= n_true * n_pred <= ES_CONFUSION_MAX_CELLS. */
+#define ES_KMEANS_MAX_ROWS (1 << 24)
+#define ES_KMEANS_MAX_COLS 4096
+#define ES_KMEANS_MAX_K 64
+#define ES_CONFUSION_MAX_CELLS 4096
+int es_kmeans_trials(int K);
+size_t es_kmeans_workspace(int rows, int cols, int K);
+size_t es_kmeans_plusplus_workspace(int rows, int cols, int K);
+int es_kmeans_assign(const void* x, int x_f64, int64_t ld, int rows, int cols, const double* centres /* [K, cols] */,
+                     int K, const int32_t* label_old /* [rows] or NULL */, int32_t* label /* [rows] */,
+                     double* dist /* [rows] */, int64_t* changed /* [1] */, double* inertia /* [1] */, void* work,
+                     size_t work_bytes, es_stream_t stream);
+int es_kmeans_update(const void* x, int x_f64, int64_t ld, int rows, int cols, const int32_t* label,
+                     const double* dist, const double* centres_old, int K, double* centres_new /* [K, cols] */,
+                     double* shift /* [1] */, void* work, size_t work_bytes, es_stream_t stream);
+int es_kmeans_plusplus(const void* x, int x_f64, int64_t ld, int rows, int cols, int K,
+                       const double* u /* [K, trials] */, int trials, double* centres /* [K, cols] */,
+                       int32_t* index /* [K] */, void* work, size_t work_bytes, es_stream_t stream);
+int es_confusion_matrix(const int32_t* pred, const int32_t* target, int64_t n, int n_true, int n_pred,
+                        int64_t* counts /* [n_true, n_pred] */, int64_t* invalid /* [1] */, es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
  * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
  * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
