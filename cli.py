@@ -8,7 +8,10 @@ The reference's CUDA_LAUNCH_BLOCKING / cudnn flags / anomaly detection (cli.py:2
 Simulation (conditions in, calorimeter images out; MoEWrapper.simulate) from a saved checkpoint:
     python cli.py -o model.architecture=neutron dataset.input_image_shape=[44,44] model.n_experts=3 \
         --simulate --checkpoint DIR [--checkpoint-epoch E] (--cond FILE.npy | --num-samples N) --out FILE.npz \
-        [--features]
+        [--features] [--real FILE.npy [--prdc-k K]]
+--real FILE.npy (real images [N,H,W] in the log1p domain, aligned with --cond) adds the sample-level precision /
+recall / density / coverage of the simulated images against them at K neighbours (default 5), jointly and per
+expert (expertsim/train/fidelity.py), as prdc_* entries of the .npz and on stdout.
 
 Dataset preparation (raw responses + particle conditions in, the three pickles of dataset.source=pickle out;
 expertsim/utils/data_preparation.py) for the detector named by dataset.zdc_type:
@@ -55,6 +58,10 @@ def parse_args(args=None):
     g.add_argument("--sim-batch-size", type=int, default=None, help="conditions per chunk")
     g.add_argument("--features", action="store_true",
                    help="also write the shower-shape observables: features [N,5], peak [N,2]")
+    g.add_argument("--real", type=str, default=None,
+                   help=".npy real images [N,H,W] (log1p domain, aligned with --cond): also precision / recall / "
+                        "density / coverage of the simulated images against them")
+    g.add_argument("--prdc-k", type=int, default=5, help="neighbours of the --real metrics")
     x = p.add_argument_group("expert diagnostics (instead of training)")
     x.add_argument("--diagnose", action="store_true",
                    help="per-expert histograms and KDEs for --conditions FILE from --checkpoint DIR, written to --out")
@@ -129,6 +136,20 @@ def simulate(args):
     res = moe.simulate(torch.from_numpy(cond), seed=args.seed, batch_size=args.sim_batch_size, sums=True,
                        features=args.features)
     extra = {k: res[k].cpu().numpy() for k in ("features", "peak")} if args.features else {}
+    if args.real is not None:
+        from expertsim.train.fidelity import prdc
+        real = np.load(args.real).astype(np.float32)
+        if real.shape[0] != cond.shape[0]:
+            raise SystemExit(f"--real has {real.shape[0]} images for {cond.shape[0]} conditions")
+        device = res["images"].device
+        m = prdc(torch.from_numpy(real).to(device), torch.log1p(res["images"]), k=args.prdc_k,
+                 expert=res["expert"], n_experts=moe.n_experts, details=True)
+        for name, v in m.items():
+            if isinstance(v, float):
+                extra[f"prdc_{name}"] = np.float64(v)
+                logger.info("prdc_%s = %.6f", name, v)
+        extra["prdc_totals"] = m["totals"].cpu().numpy()
+        extra["prdc_k"] = np.int64(args.prdc_k)
     np.savez(args.out, images=res["images"].cpu().numpy(), expert=res["expert"].cpu().numpy(),
              sums=res["sums"].cpu().numpy(), cond=cond, **extra)
     logger.info("Simulated %d images (epoch %d checkpoint) -> %s", cond.shape[0], epoch, args.out)

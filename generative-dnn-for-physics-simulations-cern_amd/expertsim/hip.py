@@ -228,6 +228,11 @@ _SIGS = {
     "es_kmeans_plusplus": (C.c_int, [P, C.c_int, I64, C.c_int, C.c_int, C.c_int, P, C.c_int, P, P, P, C.c_size_t,
                                      P]),
     "es_confusion_matrix": (C.c_int, [P, P, I64, C.c_int, C.c_int, P, P, P]),
+    "es_knn_radius_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "es_prdc_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "es_knn_radius": (C.c_int, [P, I64, C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, P, C.c_size_t, P]),
+    "es_prdc_count": (C.c_int, [P, I64, C.c_int, P, P, C.c_int, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int,
+                                C.c_int, P, P, P, P, P, P, P, C.c_size_t, P]),
 }
 
 # es_group_diversity's split of a large group (ES_PREP_SPLIT_MIN / ES_PREP_CHUNKS of include/expertsim_hip.h)
@@ -256,6 +261,23 @@ KMEANS_MAX_ROWS = 1 << 24
 KMEANS_MAX_COLS = 4096
 KMEANS_MAX_K = 64
 CONFUSION_MAX_CELLS = 4096
+
+
+# sample-level fidelity (ES_KNN_* of include/expertsim_hip.h)
+KNN_MAX_K = 16
+KNN_MAX_ROWS = 1 << 20
+KNN_MAX_COLS = 4096
+KNN_MAX_SEG = 65
+
+
+def knn_radius_workspace(n_seg: int, cap: int, k: int) -> int:
+    """Bytes of es_knn_radius's workspace (0: outside the limits)."""
+    return int(lib().es_knn_radius_workspace(int(n_seg), int(cap), int(k)))
+
+
+def prdc_workspace(n_seg: int, r_cap: int, f_cap: int) -> int:
+    """Bytes of es_prdc_count's workspace (0: outside the limits)."""
+    return int(lib().es_prdc_workspace(int(n_seg), int(r_cap), int(f_cap)))
 
 
 def kmeans_workspace(rows: int, cols: int, k: int) -> int:

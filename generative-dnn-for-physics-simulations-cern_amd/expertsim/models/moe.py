@@ -633,7 +633,7 @@ class MoEWrapper(nn.Module):
 
     @torch.no_grad()
     def evaluate_device(self, epoch, y_test, x_test, cfg, *, seed=0, sample_offset=0, routing="sample",
-                        fused=True, graph=True, details=False, features=False):
+                        fused=True, graph=True, details=False, features=False, prdc=False, prdc_k=5):
         """The metrics of evaluate (same keys) from the simulate path, without a host round trip until
         the result: real sums by es_channel_sums, repetition j of the n_calc = min(epoch // 5 + 1, 5) by
         simulate(sums=True) -- j = 0 with simulate's own noise draw, j > 0 with es_randn_dev(seed + j) on
@@ -655,7 +655,15 @@ class MoEWrapper(nn.Module):
         ws_feature_summary: ws_feat_<name> / ws_feat_std_<name> (mean / std over the repetitions of the
         joint distance) and ws_feat_<name>_<e> (expert e, mean over the repetitions); details=True adds
         feat_real [N, 5], feat_gen [R, N, 5], ws_feat [R, E + 1, 5].  The other keys keep their values bit
-        for bit."""
+        for bit.
+
+        prdc=True adds the sample-level metrics of train.fidelity.prdc at prdc_k neighbours: the real side is x
+        as given (the log1p domain), the generated side log1p of repetition 0's images from the same simulate
+        call, the segments those of the same expert vector: prdc_precision / prdc_recall / prdc_density /
+        prdc_coverage (joint) and prdc_<name>_<e> (expert e; NaN when either side has at most prdc_k rows
+        there).  The integer totals cross to the host in a second small copy; details=True adds prdc_totals
+        [E + 1, 8] and the radii.  These metrics depend on N and on prdc_k: compare equal settings only.  The
+        other keys keep their values bit for bit."""
         from ..train.utils import (FEATURE_NAMES, channel_sums, image_features, ws_across_experts_device,
                                    ws_feature_summary, ws_summary)
         dev = next(self.parameters()).device
@@ -690,6 +698,8 @@ class MoEWrapper(nn.Module):
                     feat_gen[j].copy_(sim["features"])
                 if expert is None:
                     expert = sim["expert"]
+                if prdc and j == 0:
+                    gen_log = torch.log1p(sim["images"])
             ws = ws_across_experts_device(sums_real, sums_gen, expert, E)
             if features:
                 ws_feat = ws_across_experts_device(feat_real, feat_gen, expert, E)
@@ -707,6 +717,16 @@ class MoEWrapper(nn.Module):
                 log[f"ws_feat_std_{name}"] = f_std[k]
                 for e in range(E):
                     log[f"ws_feat_{name}_{e}"] = f_exp[e, k]
+        if prdc:
+            from ..train import fidelity
+            with torch.cuda.device(dev):
+                raw = fidelity.prdc_device(x, gen_log, int(prdc_k), expert, E)
+                totals = raw["totals"].cpu().numpy()                                  # the second, small D2H copy
+            for name, v in fidelity.metrics_dict(totals, int(prdc_k), True).items():
+                log[f"prdc_{name}"] = v
+            if details:
+                log.update(prdc_totals=raw["totals"], prdc_r_radius2=raw["r_radius2"],
+                           prdc_f_radius2=raw["f_radius2"])
         if details:
             log.update(sums_real=sums_real, sums_gen=sums_gen, expert=expert, ws=ws)
             if features:

@@ -110,11 +110,21 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     diagnostics_epoch_<epoch>.npz there.  Off: the returned dict and the launches are unchanged.
     train.eval_embedding (with eval_diagnostics only): diagnose(embedding=True, embedding_iters=
     train.eval_embedding_iters, embedding_max=train.eval_embedding_max) -- the PCA / t-SNE keys of
-    train/embedding.py join the diagnostics and the .npz."""
+    train/embedding.py join the diagnostics and the .npz.
+    train.eval_prdc (with eval_on_device only): also the sample-level precision / recall / density / coverage of
+    evaluate_device(prdc=True, prdc_k=train.eval_prdc_k), each key averaged over the batches in which it is finite
+    (an expert with at most k rows in a batch gives NaN there); NaN if it is finite in none.  These metrics
+    depend on the batch size (the number of samples on each side) and on k, so runs are comparable only at equal
+    batch size and equal train.eval_prdc_k."""
     on_device = bool(cfg.train.get("eval_on_device", False))
     features = bool(cfg.train.get("eval_features", False))
     diagnostics = bool(cfg.train.get("eval_diagnostics", False))
     embedding = bool(cfg.train.get("eval_embedding", False))
+    prdc = bool(cfg.train.get("eval_prdc", False))
+    prdc_k = int(cfg.train.get("eval_prdc_k", 5))
+    if prdc and not on_device:
+        raise ValueError("train.eval_prdc needs train.eval_on_device: the sample-level metrics exist on the device "
+                         "path only (MoEWrapper.evaluate_device)")
     if embedding and not diagnostics:
         raise ValueError("train.eval_embedding needs train.eval_diagnostics: the embedding is part of the expert "
                          "diagnostics (MoEWrapper.diagnose(embedding=True))")
@@ -131,7 +141,12 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
         from .utils import FEATURE_NAMES
         for name in FEATURE_NAMES:
             keys += [f"ws_feat_{name}", f"ws_feat_std_{name}", *[f"ws_feat_{name}_{i}" for i in range(moe.n_experts)]]
-    acc: Dict[str, List[float]] = {k: [] for k in keys}
+    prdc_keys = []
+    if prdc:
+        from .fidelity import METRICS
+        prdc_keys = [f"prdc_{name}" for name in METRICS]
+        prdc_keys += [f"prdc_{name}_{i}" for i in range(moe.n_experts) for name in METRICS]
+    acc: Dict[str, List[float]] = {k: [] for k in keys + prdc_keys}
     seen = 0                                   # test samples in earlier batches
     conds = []                                 # the batches' device conditions (eval_diagnostics)
     for b, batch in enumerate(test_loader):
@@ -140,9 +155,10 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
         real_images, _, cond, std, intensity, true_positions = batch
         if on_device:
             cond_dev = cond.to(device)
+            extra = dict(prdc=True, prdc_k=prdc_k) if prdc else {}
             m = moe.evaluate_device(epoch, cond_dev, real_images, cfg,
                                     seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=seen,
-                                    features=features)
+                                    features=features, **extra)
             if diagnostics:
                 conds.append(cond_dev)
             seen += int(cond.shape[0])
@@ -150,7 +166,11 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
             m = moe.evaluate(epoch, cond.to(device), real_images, true_positions, std, intensity, cfg, device)
         for k in keys:
             acc[k].append(float(m[k]))
-    out = {k: (sum(v) / len(v) if v else 0.0) for k, v in acc.items()}
+        for k in prdc_keys:
+            if np.isfinite(m[k]):
+                acc[k].append(float(m[k]))
+    out = {k: (sum(acc[k]) / len(acc[k]) if acc[k] else 0.0) for k in keys}
+    out.update({k: (sum(acc[k]) / len(acc[k]) if acc[k] else float("nan")) for k in prdc_keys})
     if diagnostics and conds:
         from .diagnostics import save_diagnostics
         extra = dict(embedding=True, embedding_iters=int(cfg.train.get("eval_embedding_iters", 1000)),

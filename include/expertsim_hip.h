@@ -1057,6 +1057,68 @@ int es_confusion_matrix(const int32_t* pred, const int32_t* target, int64_t n, i
                         int64_t* counts /* [n_true, n_pred] */, int64_t* invalid /* [1] */, es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sample-level fidelity and diversity: the k-nearest-neighbour radii and the counts behind precision / recall
+ * (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020, the `prdc` package) -- csrc/fidelity.hip.
+ * ---------------------------------------------------------------------------------------- */
+/* x [rows][ld] fp32 with unit column stride, of which the first `cols` columns count.  1 <= rows <= ES_KNN_MAX_ROWS,
+ * 1 <= cols <= ES_KNN_MAX_COLS, cols <= ld, 1 <= k <= ES_KNN_MAX_K, 1 <= n_seg <= ES_KNN_MAX_SEG,
+ * 1 <= cap <= ES_KNN_MAX_ROWS.  Every pointer is a DEVICE pointer; no host sync, everything runs on `stream`.
+ * Values must be finite.  Outside the limits, with a NULL required pointer or too small a workspace: ES_ERR_ARG
+ * before any launch, and nothing is written.
+ *
+ * Segments follow es_wasserstein_1d: segment s of a side covers the rows idx[seg[2s] .. seg[2s+1]) (idx NULL: the
+ * rows themselves); idx (when given) has `rows` entries; the bounds are clamped to [0, rows], a segment's length to
+ * `cap` (the host upper bound that sizes grids, outputs and workspaces) and every row index to [0, rows).  Segments
+ * may overlap (the joint distribution plus one per expert).  Lengths are read on the device: grids are sized from
+ * `cap` and tiles past the live length exit.
+ *
+ * d2(a, b), the squared distance of two rows, is the sum of squared differences in column order:
+ *   s = +0.0; for c = 0, 1, .., cols - 1 in order: t = (double)a[c] - (double)b[c]; q = t * t; s = s + q.
+ * Every operation is rounded (no contraction, no FMA) and one pair's sum is walked by one thread, so d2 does not
+ * depend on how the rows are tiled.  It is NOT the |a|^2 - 2 a.b + |b|^2 expansion scikit-learn uses, which cancels
+ * exactly where these metrics matter (near-duplicate images of a collapsed generator): d2(a, a) is exactly 0,
+ * d2(a, b) == d2(b, a) bitwise and equal rows are at equal distances from everything.
+ *
+ * es_knn_radius.  radius2[s][p] (fp64 [n_seg][cap]), p < L_s = the segment's length: the (k+1)-th smallest value of
+ * the multiset { d2(x_p, x_q) : q in segment s }, q = p included (prdc's "k-th neighbour, self included at distance
+ * 0").  L_s <= k: there is no such value and the entries p < L_s are +inf.  Entries at p >= L_s are not written.
+ * Only the value is selected, so the result depends on neither the tiling nor the merge order.
+ * work: es_knn_radius_workspace(n_seg, cap, k) bytes (0: outside the limits): the partial lists
+ * [n_seg][cap][split][k + 1] fp64 when the other side's tiles are cut into split > 1 runs.
+ *
+ * es_prdc_count.  real / fake have their own ld / rows / idx / seg / cap and share cols and n_seg; r_radius2
+ * [n_seg][r_cap] and f_radius2 [n_seg][f_cap] are es_knn_radius's of each side at the same segments.  For segment s
+ * with real members p < n_r and generated members q < n_f:
+ *   f_count[s][q] (int32 [n_seg][f_cap]) = #{ p : d2(r_p, f_q) < r_radius2[s][p] }
+ *   r_hit[s][p]   (int32 [n_seg][r_cap]) = 1 if some q has d2(r_p, f_q) < f_radius2[s][q], else 0
+ *   r_min2[s][p]  (fp64  [n_seg][r_cap]) = min_q d2(r_p, f_q)  (+inf when n_f == 0)
+ *   totals[s]     (int64 [n_seg][8])     = { n_r, n_f, valid, precision_hits, recall_hits, density_pairs,
+ *                                            coverage_hits, 0 }
+ *     valid = (n_r > k && n_f > k); precision_hits = #{ q : f_count > 0 }; recall_hits = sum_p r_hit;
+ *     density_pairs = sum_q f_count; coverage_hits = #{ p : r_min2 < r_radius2 }; all four are 0 when the segment
+ *     is not valid (the per-row outputs follow the formulas whatever the radii hold).
+ * Comparisons are strict and on squared distances (prdc compares the square roots: the same in exact arithmetic).
+ * Entries at p >= n_r / q >= n_f are not written; f_count, r_hit and r_min2 may each be NULL.  Reductions are
+ * integer adds / ors and minima of non-negative doubles (an unsigned integer minimum on the bit pattern), by vector
+ * atomics on the workspace: no order matters and a rerun is bit-equal.  precision = precision_hits / n_f,
+ * recall = recall_hits / n_r, density = density_pairs / (k n_f), coverage = coverage_hits / n_r are left to the host.
+ * work: es_prdc_workspace(n_seg, r_cap, f_cap) bytes (0: outside the limits): the three per-row arrays. */
+#define ES_KNN_MAX_K 16
+#define ES_KNN_MAX_ROWS (1 << 20)
+#define ES_KNN_MAX_COLS 4096
+#define ES_KNN_MAX_SEG 65
+size_t es_knn_radius_workspace(int n_seg, int cap, int k);
+size_t es_prdc_workspace(int n_seg, int r_cap, int f_cap);
+int es_knn_radius(const float* x, int64_t ld, int rows, int cols, const int32_t* idx /* [rows] or NULL */,
+                  const int32_t* seg /* [n_seg, 2] */, int n_seg, int cap, int k, double* radius2 /* [n_seg, cap] */,
+                  void* work, size_t work_bytes, es_stream_t stream);
+int es_prdc_count(const float* real, int64_t r_ld, int r_rows, const int32_t* r_idx, const int32_t* r_seg, int r_cap,
+                  const float* fake, int64_t f_ld, int f_rows, const int32_t* f_idx, const int32_t* f_seg, int f_cap,
+                  int cols, int n_seg, int k, const double* r_radius2, const double* f_radius2,
+                  int32_t* f_count /* or NULL */, int32_t* r_hit /* or NULL */, double* r_min2 /* or NULL */,
+                  int64_t* totals /* [n_seg, 8] */, void* work, size_t work_bytes, es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
  * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
  * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
