@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "segment.h"
 
 namespace {
 
@@ -53,7 +54,7 @@ int km_chunks(int rows, int cols, int K) {
   return c > 1 ? c : 1;
 }
 int km_tiles(int cols) { return (cols + KM_TILE - 1) / KM_TILE; }
-size_t km_align(size_t b) { return (b + 15) & ~(size_t)15; }
+constexpr size_t KM_ALIGN = 16;             // of every array of a workspace
 
 // ------------------------------------------------------------------------------------------ distances
 // PP = false: label / dist of the nearest centre (the lowest index wins a tie).
@@ -470,20 +471,14 @@ struct KmWork {
 };
 KmWork km_work(void* base, int rows, int cols, int K) {
   const int nred = km_red_chunks(rows);
-  char* p = (char*)base;
+  Carver c(base, KM_ALIGN);
   KmWork w;
-  size_t o = 0;
-  w.red = (double*)(p + o);
-  o += km_align((size_t)KM_MAX_TRIALS * nred * sizeof(double));
-  w.cpart = (int64_t*)(p + o);
-  o += km_align((size_t)nred * sizeof(int64_t));
-  w.partial = (double*)(p + o);
-  o += km_align((size_t)km_chunks(rows, cols, K) * K * cols * sizeof(double));
-  w.shift_part = (double*)(p + o);
-  o += km_align((size_t)K * km_tiles(cols) * sizeof(double));
-  w.meta = (int32_t*)(p + o);
-  o += km_align((size_t)KM_META * sizeof(int32_t));
-  w.bytes = o;
+  w.red = c.take<double>((size_t)KM_MAX_TRIALS * nred);
+  w.cpart = c.take<int64_t>((size_t)nred);
+  w.partial = c.take<double>((size_t)km_chunks(rows, cols, K) * K * cols);
+  w.shift_part = c.take<double>((size_t)K * km_tiles(cols));
+  w.meta = c.take<int32_t>((size_t)KM_META);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -498,22 +493,15 @@ struct PpWork {
 };
 PpWork pp_work(void* base, int rows, int cols) {
   const int nred = km_red_chunks(rows);
-  char* p = (char*)base;
+  Carver c(base, KM_ALIGN);
   PpWork w;
-  size_t o = 0;
-  w.red = (double*)(p + o);
-  o += km_align((size_t)KM_MAX_TRIALS * nred * sizeof(double));
-  w.cc = (double*)(p + o);
-  o += km_align((size_t)KM_MAX_TRIALS * cols * sizeof(double));
-  w.cdist = (double*)(p + o);
-  o += km_align((size_t)KM_MAX_TRIALS * rows * sizeof(double));
-  w.closest = (double*)(p + o);
-  o += km_align((size_t)rows * sizeof(double));
-  w.pot = (double*)(p + o);
-  o += km_align((size_t)KM_MAX_TRIALS * sizeof(double));
-  w.cand = (int32_t*)(p + o);
-  o += km_align((size_t)KM_MAX_TRIALS * sizeof(int32_t));
-  w.bytes = o;
+  w.red = c.take<double>((size_t)KM_MAX_TRIALS * nred);
+  w.cc = c.take<double>((size_t)KM_MAX_TRIALS * cols);
+  w.cdist = c.take<double>((size_t)KM_MAX_TRIALS * rows);
+  w.closest = c.take<double>((size_t)rows);
+  w.pot = c.take<double>((size_t)KM_MAX_TRIALS);
+  w.cand = c.take<int32_t>((size_t)KM_MAX_TRIALS);
+  w.bytes = c.bytes();
   return w;
 }
 

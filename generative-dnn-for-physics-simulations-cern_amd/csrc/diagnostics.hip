@@ -36,6 +36,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "segment.h"
 
 namespace {
 
@@ -46,30 +47,6 @@ constexpr int DIAG_STAGE = 2048;          // doubles of a parked tile: 16 KiB
 constexpr int DIAG_PEEL = 3;              // distinct bins a wave aggregates before the per-lane adds
 constexpr int DIAG_RANGE_BLOCKS = 256;
 constexpr double DIAG_SQRT_2PI = 2.5066282746310002;
-
-struct DiagSeg { int b, n; };
-__device__ __forceinline__ DiagSeg diag_seg(const int32_t* seg, int s, int rows, int cap) {
-  int b = seg[2 * s], e = seg[2 * s + 1];
-  b = b < 0 ? 0 : (b > rows ? rows : b);
-  e = e < b ? b : (e > rows ? rows : e);
-  const int n = e - b;
-  return {b, n > cap ? cap : n};
-}
-// the row of position p (0 <= p < rows) of idx, clamped to [0, rows)
-__device__ __forceinline__ int diag_row(const int32_t* idx, int p, int rows) {
-  if (idx == nullptr) return p;
-  const int r = idx[p];
-  return r < 0 ? 0 : (r >= rows ? rows - 1 : r);
-}
-
-// order-preserving key of a finite double: a < b  <=>  key(a) < key(b) as unsigned integers
-__device__ __forceinline__ unsigned long long diag_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double diag_unkey(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
 
 // rng[c] = min key, rng[ES_DIAG_MAX_COLS + c] = max key (initialised to all ones / zero on the stream)
 template <typename T>
@@ -87,7 +64,7 @@ __global__ void __launch_bounds__(DIAG_THREADS) diag_range_kernel(const T* __res
   if (r0 < rpp) {
     unsigned long long lo = ~0ull, hi = 0ull;
     for (int64_t r = (int64_t)blockIdx.x * rpp + r0; r < rows; r += (int64_t)gridDim.x * rpp) {
-      const unsigned long long k = diag_key((double)x[r * ld + c]);
+      const unsigned long long k = f64_key((double)x[r * ld + c]);
       lo = k < lo ? k : lo;
       hi = k > hi ? k : hi;
     }
@@ -111,7 +88,7 @@ __global__ void __launch_bounds__(DIAG_THREADS) diag_linspace_kernel(const unsig
   const int i = blockIdx.x * DIAG_THREADS + threadIdx.x;
   if (i >= cols * num) return;
   const int c = i / num, k = i - c * num;
-  double lo = diag_unkey(rng[c]), hi = diag_unkey(rng[ES_DIAG_MAX_COLS + c]);
+  double lo = f64_unkey(rng[c]), hi = f64_unkey(rng[ES_DIAG_MAX_COLS + c]);
   if (widen && lo == hi) {
     lo = lo - 1e-6;
     hi = hi + 1e-6;
@@ -148,7 +125,7 @@ __global__ void __launch_bounds__(DIAG_THREADS) diag_hist_kernel(const T* __rest
   int* sh_o = sh_h + cols * bins;                               // [cols]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int s = blockIdx.y;
-  const DiagSeg sg = diag_seg(seg, s, rows, seg_cap);
+  const SegSpan sg = seg_span(seg, s, rows, seg_cap);
   const int p0 = blockIdx.x * tile_rows;
   if (p0 >= sg.n) return;                                       // block-uniform, before any barrier
   const int live = sg.n - p0 < tile_rows ? sg.n - p0 : tile_rows;
@@ -156,7 +133,7 @@ __global__ void __launch_bounds__(DIAG_THREADS) diag_hist_kernel(const T* __rest
   for (int i = tid; i < cols * bins + cols; i += DIAG_THREADS) sh_h[i] = 0;      // the histograms and sh_o
   for (int i = tid; i < live * cols; i += DIAG_THREADS) {
     const int r = i / cols, c = i - r * cols;
-    const int row = diag_row(idx, sg.b + p0 + r, rows);
+    const int row = seg_row(idx, sg.b + p0 + r, rows);
     sh_x[r * pitch + c] = (double)x[(int64_t)row * ld + c];
   }
   __syncthreads();
@@ -218,7 +195,7 @@ __global__ void __launch_bounds__(DIAG_THREADS) diag_moments_kernel(const T* __r
   __shared__ double part[ES_PREP_CHUNKS][ES_DIAG_MAX_COLS];
   __shared__ double mean[ES_DIAG_MAX_COLS];
   const int tid = threadIdx.x, s = blockIdx.x;
-  const DiagSeg sg = diag_seg(seg, s, rows, seg_cap);
+  const SegSpan sg = seg_span(seg, s, rows, seg_cap);
   const int n = sg.n;
   const int L = n <= ES_PREP_SPLIT_MIN ? n : (n + ES_PREP_CHUNKS - 1) / ES_PREP_CHUNKS;
   const double dn = (double)n;
@@ -230,7 +207,7 @@ __global__ void __launch_bounds__(DIAG_THREADS) diag_moments_kernel(const T* __r
       const double m = pass ? mean[c] : 0.0;
       double acc = 0.0;
       for (int p = lo; p < hi; ++p) {
-        const double v = (double)x[(int64_t)diag_row(idx, sg.b + p, rows) * ld + c];
+        const double v = (double)x[(int64_t)seg_row(idx, sg.b + p, rows) * ld + c];
         if (pass) {
           const double d = v - m;
           const double q = d * d;
@@ -280,12 +257,12 @@ __global__ void __launch_bounds__(DIAG_THREADS) diag_kde_kernel(const T* __restr
 #pragma clang fp contract(off)
   __shared__ double mem[ES_DIAG_KDE_CHUNK];
   const int tid = threadIdx.x, ch = blockIdx.x, c = blockIdx.y, s = blockIdx.z;
-  const DiagSeg sg = diag_seg(seg, s, rows, seg_cap);
+  const SegSpan sg = seg_span(seg, s, rows, seg_cap);
   const int first = ch * ES_DIAG_KDE_CHUNK;
   if (first >= sg.n || valid[(int64_t)s * cols + c] == 0) return;   // block-uniform, before the barrier
   const int cnt = sg.n - first < ES_DIAG_KDE_CHUNK ? sg.n - first : ES_DIAG_KDE_CHUNK;
   for (int i = tid; i < cnt; i += blockDim.x)
-    mem[i] = (double)x[(int64_t)diag_row(idx, sg.b + first + i, rows) * ld + c];
+    mem[i] = (double)x[(int64_t)seg_row(idx, sg.b + first + i, rows) * ld + c];
   __syncthreads();
   const double r = 1.0 / bw[(int64_t)s * cols + c];
   double* out = partial + (((int64_t)s * cols + c) * nchunks + ch) * points;
@@ -310,7 +287,7 @@ __global__ void __launch_bounds__(DIAG_THREADS) diag_kde_close_kernel(const int3
                                                                       double* __restrict__ density) {
 #pragma clang fp contract(off)
   const int c = blockIdx.x, s = blockIdx.y;
-  const DiagSeg sg = diag_seg(seg, s, rows, seg_cap);
+  const SegSpan sg = seg_span(seg, s, rows, seg_cap);
   const int64_t sc = (int64_t)s * cols + c;
   const bool ok = valid[sc] != 0;
   const int used = (sg.n + ES_DIAG_KDE_CHUNK - 1) / ES_DIAG_KDE_CHUNK;
@@ -336,6 +313,23 @@ bool diag_hist_ok(int cols, int bins) {
 }
 int diag_chunks(int seg_cap) { return (seg_cap + ES_DIAG_KDE_CHUNK - 1) / ES_DIAG_KDE_CHUNK; }
 
+// Both workspaces start with the range keys [2][ES_DIAG_MAX_COLS] (ES_DIAG_RANGE_BYTES); the KDE's chunk sums
+// [n_seg][cols][chunks][points] follow.  points == 0: the histogram's.
+struct DiagWork {
+  unsigned long long* rng;
+  double* partial;
+  size_t bytes;
+};
+static_assert(ES_DIAG_RANGE_BYTES == 2 * ES_DIAG_MAX_COLS * sizeof(unsigned long long), "the range keys");
+DiagWork diag_work(void* base, int n_seg, int cols, int chunks, int points) {
+  Carver c(base, sizeof(double));
+  DiagWork w;
+  w.rng = c.take<unsigned long long>(2 * ES_DIAG_MAX_COLS);
+  w.partial = c.take<double>((size_t)n_seg * cols * chunks * points);
+  w.bytes = c.bytes();
+  return w;
+}
+
 // the range of every column into rng, then linspace(lo, hi, num) into out
 void diag_range_linspace(const void* x, int x_f64, int64_t ld, int rows, int cols, int num, int widen,
                          unsigned long long* rng, double* out, hipStream_t st) {
@@ -353,7 +347,7 @@ void diag_range_linspace(const void* x, int x_f64, int64_t ld, int rows, int col
 }  // namespace
 
 extern "C" size_t es_segment_histogram_workspace(int cols, int bins) {
-  return diag_hist_ok(cols, bins) ? (size_t)ES_DIAG_RANGE_BYTES : 0;
+  return diag_hist_ok(cols, bins) ? diag_work(nullptr, 0, 0, 0, 0).bytes : 0;
 }
 
 extern "C" int es_segment_histogram(const void* x, int x_f64, int64_t ld, int rows, int cols, const int32_t* idx,
@@ -378,7 +372,7 @@ extern "C" int es_segment_histogram(const void* x, int x_f64, int64_t ld, int ro
     if (edges != edges_out)
       (void)hipMemcpyAsync(edges_out, edges, (size_t)cols * (bins + 1) * sizeof(double), hipMemcpyDeviceToDevice, st);
   } else {
-    diag_range_linspace(x, x_f64, ld, rows, cols, bins + 1, 0, (unsigned long long*)work, edges_out, st);
+    diag_range_linspace(x, x_f64, ld, rows, cols, bins + 1, 0, diag_work(work, 0, 0, 0, 0).rng, edges_out, st);
   }
   const int pitch = cols | 1;
   const int fit = DIAG_STAGE / pitch;
@@ -402,7 +396,7 @@ extern "C" size_t es_segment_kde_workspace(int n_seg, int cols, int points, int 
       points > ES_DIAG_KDE_MAX_POINTS || seg_cap < 1)
     return 0;
   const int cap = seg_cap < DIAG_MAX_ROWS ? seg_cap : DIAG_MAX_ROWS;
-  return (size_t)ES_DIAG_RANGE_BYTES + (size_t)n_seg * cols * diag_chunks(cap) * points * sizeof(double);
+  return diag_work(nullptr, n_seg, cols, diag_chunks(cap), points).bytes;
 }
 
 extern "C" int es_segment_kde(const void* x, int x_f64, int64_t ld, int rows, int cols, const int32_t* idx,
@@ -422,13 +416,13 @@ extern "C" int es_segment_kde(const void* x, int x_f64, int64_t ld, int rows, in
   const size_t need = es_segment_kde_workspace(n_seg, cols, points, cap);
   ES_CHECK_ARG(work && work_bytes >= need, "segment_kde: workspace of %zu bytes, %zu needed", work_bytes, need);
   const hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)((char*)work + ES_DIAG_RANGE_BYTES);
   const int nchunks = diag_chunks(cap);
+  const DiagWork w = diag_work(work, n_seg, cols, nchunks, points);
   if (grid) {
     if (grid != grid_out)
       (void)hipMemcpyAsync(grid_out, grid, (size_t)cols * points * sizeof(double), hipMemcpyDeviceToDevice, st);
   } else {
-    diag_range_linspace(x, x_f64, ld, rows, cols, points, 1, (unsigned long long*)work, grid_out, st);
+    diag_range_linspace(x, x_f64, ld, rows, cols, points, 1, w.rng, grid_out, st);
   }
   const int lanes = points < DIAG_THREADS ? ((points + 63) / 64) * 64 : DIAG_THREADS;
   const dim3 gm(n_seg), gk(nchunks, cols, n_seg), gc(cols, n_seg), block(DIAG_THREADS), bk(lanes);
@@ -436,14 +430,14 @@ extern "C" int es_segment_kde(const void* x, int x_f64, int64_t ld, int rows, in
     hipLaunchKernelGGL(diag_moments_kernel<double>, gm, block, 0, st, (const double*)x, ld, rows, cols, idx, seg, cap,
                        min_samples, std_eps, bw, valid, sd);
     hipLaunchKernelGGL(diag_kde_kernel<double>, gk, bk, 0, st, (const double*)x, ld, rows, cols, idx, seg, cap, points,
-                       grid_out, bw, valid, nchunks, partial);
+                       grid_out, bw, valid, nchunks, w.partial);
   } else {
     hipLaunchKernelGGL(diag_moments_kernel<float>, gm, block, 0, st, (const float*)x, ld, rows, cols, idx, seg, cap,
                        min_samples, std_eps, bw, valid, sd);
     hipLaunchKernelGGL(diag_kde_kernel<float>, gk, bk, 0, st, (const float*)x, ld, rows, cols, idx, seg, cap, points,
-                       grid_out, bw, valid, nchunks, partial);
+                       grid_out, bw, valid, nchunks, w.partial);
   }
-  hipLaunchKernelGGL(diag_kde_close_kernel, gc, block, 0, st, seg, rows, cap, cols, points, bw, valid, nchunks, partial,
+  hipLaunchKernelGGL(diag_kde_close_kernel, gc, block, 0, st, seg, rows, cap, cols, points, bw, valid, nchunks, w.partial,
                      density);
   ES_CHECK_LAUNCH();
   return ES_OK;

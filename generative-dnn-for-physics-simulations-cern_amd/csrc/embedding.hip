@@ -28,6 +28,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "segment.h"
 
 namespace {
 
@@ -498,24 +499,21 @@ int tsne_split_len(int rows) {
   const int ns = tsne_nsplit(rows), per = (rows + ns - 1) / ns;
   return ((per + TSNE_STAGE - 1) / TSNE_STAGE) * TSNE_STAGE;
 }
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct TsneWork {
   double *part, *g, *scal;
   float *b2, *l2;
+  size_t bytes;
 };
 TsneWork tsne_carve(void* work, int rows) {
-  char* p = (char*)work;
+  Carver c(work, 256);
   TsneWork w;
-  w.part = (double*)p;
-  p += align256((size_t)tsne_nsplit(rows) * rows * TSNE_PART * sizeof(double));
-  w.g = (double*)p;
-  p += align256((size_t)rows * 2 * sizeof(double));
-  w.scal = (double*)p;
-  p += 256;
-  w.b2 = (float*)p;
-  p += align256((size_t)rows * sizeof(float));
-  w.l2 = (float*)p;
+  w.part = c.take<double>((size_t)tsne_nsplit(rows) * rows * TSNE_PART);
+  w.g = c.take<double>((size_t)rows * 2);
+  w.scal = c.take<double>(3);             // Z, KL, sum p_ij
+  w.b2 = c.take<float>((size_t)rows);
+  w.l2 = c.take<float>((size_t)rows);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -590,8 +588,7 @@ extern "C" int es_tsne_affinities(const float* x, int64_t ld, int rows, int cols
 
 extern "C" size_t es_tsne_workspace(int rows) {
   if (rows < 2 || rows > TSNE_MAX_ROWS) return 0;
-  return align256((size_t)tsne_nsplit(rows) * rows * TSNE_PART * sizeof(double)) +
-         align256((size_t)rows * 2 * sizeof(double)) + 256 + 2 * align256((size_t)rows * sizeof(float));
+  return tsne_carve(nullptr, rows).bytes;
 }
 
 extern "C" int es_tsne_gradient(const float* x, int64_t ld, int rows, int cols, const double* beta,

@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "segment.h"
 
 namespace {
 
@@ -57,21 +58,10 @@ struct FdArgs {
   unsigned long long* mn;                   //   [n_seg][a.cap], the bits of a non-negative double
 };
 
-// one side of one segment: first position and length, clamped to the rows and to the cap (es_wasserstein_1d's rule)
-struct FdSeg { int b, n; };
-__device__ __forceinline__ FdSeg fd_seg(const FdSide& sd, int s) {
-  int b = sd.seg[2 * s], e = sd.seg[2 * s + 1];
-  b = b < 0 ? 0 : (b > sd.rows ? sd.rows : b);
-  e = e < b ? b : (e > sd.rows ? sd.rows : e);
-  const int n = e - b;
-  return {b, n < sd.cap ? n : sd.cap};
-}
+__device__ __forceinline__ SegSpan fd_seg(const FdSide& sd, int s) { return seg_span(sd.seg, s, sd.rows, sd.cap); }
 // element offset of member i of the segment (n >= 1); a member past the end reads the last one's row
-__device__ __forceinline__ int64_t fd_off(const FdSide& sd, FdSeg sg, int i) {
-  const int m = sg.b + (i < sg.n ? i : sg.n - 1);
-  int r = sd.idx ? sd.idx[m] : m;
-  r = r < 0 ? 0 : (r >= sd.rows ? sd.rows - 1 : r);
-  return (int64_t)r * sd.ld;
+__device__ __forceinline__ int64_t fd_off(const FdSide& sd, SegSpan sg, int i) {
+  return (int64_t)seg_row(sd.idx, sg.b + (i < sg.n ? i : sg.n - 1), sd.rows) * sd.ld;
 }
 
 // sorted insertion of c < col[k] into the k + 1 ascending values col[0], col[FD_TILE], ..
@@ -100,7 +90,7 @@ __global__ void __launch_bounds__(FD_THREADS, 2) fd_pair_kernel(FdArgs g) {
 
   const int t = threadIdx.x, lane = t & 63, tx = t & 15, ty = t >> 4, grp = lane & 48;
   const int s = blockIdx.z, chunk = blockIdx.y, p0 = blockIdx.x * FD_TILE;
-  const FdSeg sa = fd_seg(g.a, s), sb = fd_seg(g.b, s);
+  const SegSpan sa = fd_seg(g.a, s), sb = fd_seg(g.b, s);
   if (p0 >= sa.n) return;                   // block-uniform: a tile past the live length
   const int k = g.k;
 
@@ -277,7 +267,7 @@ __global__ void __launch_bounds__(FD_THREADS, 2) fd_pair_kernel(FdArgs g) {
 __global__ void __launch_bounds__(FD_TILE) fd_merge_kernel(FdArgs g) {
   __shared__ double lst[FD_KK * FD_TILE];
   const int t = threadIdx.x, s = blockIdx.y, p = blockIdx.x * FD_TILE + t, k = g.k;
-  const FdSeg sa = fd_seg(g.a, s);
+  const SegSpan sa = fd_seg(g.a, s);
   if (p >= sa.n) return;
   double* col = lst + t;                    // a thread owns its column: no barrier
   for (int slot = 0; slot <= k; ++slot) col[slot * FD_TILE] = INFINITY;
@@ -300,7 +290,7 @@ __global__ void __launch_bounds__(1024) fd_totals_kernel(FdArgs g, int32_t* __re
                                                         int64_t* __restrict__ totals) {
   __shared__ unsigned long long sum[4];
   const int s = blockIdx.x, t = threadIdx.x;
-  const FdSeg sa = fd_seg(g.a, s), sb = fd_seg(g.b, s);
+  const SegSpan sa = fd_seg(g.a, s), sb = fd_seg(g.b, s);
   if (t < 4) sum[t] = 0ull;
   __syncthreads();
   unsigned long long prec = 0, rec = 0, dens = 0, cov = 0;
@@ -349,9 +339,16 @@ int fd_split(int a_cap, int b_cap) {
   sp = sp < tb ? sp : tb;
   return sp > 1 ? sp : 1;
 }
-size_t fd_align(size_t b) { return (b + 15) & ~(size_t)15; }
+constexpr size_t FD_ALIGN = 16;
 bool fd_side_ok(int rows, int cap, int n_seg) {
   return rows >= 1 && rows <= FD_MAX_ROWS && cap >= 1 && cap <= FD_MAX_ROWS && n_seg >= 1 && n_seg <= FD_MAX_SEG;
+}
+
+// es_knn_radius: the runs' lists [n_seg][cap][split][k + 1]; with one run there is nothing to merge and one
+// double stands in, so the size is never 0 inside the limits
+double* knn_lists(Carver& c, int n_seg, int cap, int k) {
+  const int split = fd_split(cap, cap);
+  return c.take<double>(split == 1 ? 1 : (size_t)n_seg * cap * split * (k + 1));
 }
 
 struct PrdcWork {
@@ -361,16 +358,12 @@ struct PrdcWork {
   size_t bytes;
 };
 PrdcWork prdc_work(void* base, int n_seg, int r_cap, int f_cap) {
-  char* p = (char*)base;
+  Carver c(base, FD_ALIGN);
   PrdcWork w;
-  size_t o = 0;
-  w.mn = (unsigned long long*)(p + o);
-  o += fd_align((size_t)n_seg * r_cap * sizeof(unsigned long long));
-  w.hit = (int32_t*)(p + o);
-  o += fd_align((size_t)n_seg * r_cap * sizeof(int32_t));
-  w.cnt = (int32_t*)(p + o);
-  o += fd_align((size_t)n_seg * f_cap * sizeof(int32_t));
-  w.bytes = o;
+  w.mn = c.take<unsigned long long>((size_t)n_seg * r_cap);
+  w.hit = c.take<int32_t>((size_t)n_seg * r_cap);
+  w.cnt = c.take<int32_t>((size_t)n_seg * f_cap);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -378,9 +371,9 @@ PrdcWork prdc_work(void* base, int n_seg, int r_cap, int f_cap) {
 
 extern "C" size_t es_knn_radius_workspace(int n_seg, int cap, int k) {
   if (!fd_side_ok(1, cap, n_seg) || k < 1 || k > FD_MAX_K) return 0;
-  const int split = fd_split(cap, cap);
-  if (split == 1) return 16;                // no lists to merge; never 0 inside the limits
-  return fd_align((size_t)n_seg * cap * split * (k + 1) * sizeof(double));
+  Carver c(nullptr, FD_ALIGN);
+  knn_lists(c, n_seg, cap, k);
+  return c.bytes();
 }
 
 extern "C" size_t es_prdc_workspace(int n_seg, int r_cap, int f_cap) {
@@ -408,7 +401,8 @@ extern "C" int es_knn_radius(const float* x, int64_t ld, int rows, int cols, con
   g.split = fd_split(cap, cap);
   g.per = (fd_tiles(cap) + g.split - 1) / g.split;
   g.radius2 = radius2;
-  g.part = (double*)work;
+  Carver c(work, FD_ALIGN);
+  g.part = knn_lists(c, n_seg, cap, k);
   hipLaunchKernelGGL(fd_pair_kernel<false>, dim3(fd_tiles(cap), g.split, n_seg), dim3(FD_THREADS), 0, st, g);
   if (g.split > 1) hipLaunchKernelGGL(fd_merge_kernel, dim3(fd_tiles(cap), n_seg), dim3(FD_TILE), 0, st, g);
   ES_CHECK_LAUNCH();

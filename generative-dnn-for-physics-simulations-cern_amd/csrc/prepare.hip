@@ -37,6 +37,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "segment.h"
 
 namespace {
 
@@ -46,17 +47,9 @@ constexpr int PREP_SPLIT_MIN = ES_PREP_SPLIT_MIN;   // above: the group's member
 constexpr int PREP_CHUNKS = ES_PREP_CHUNKS;
 constexpr int PREP_MAX_HW = 4096;
 
-struct PrepRange { int b, n; };
-// rows perm[b .. b + n) of group g, clamped to the n_rows entries of perm
-__device__ __forceinline__ PrepRange prep_range(const int32_t* offs, int g, int n_rows) {
-  int b = offs[g], e = offs[g + 1];
-  b = b < 0 ? 0 : (b > n_rows ? n_rows : b);
-  e = e < b ? b : (e > n_rows ? n_rows : e);
-  return {b, e - b};
-}
-__device__ __forceinline__ int prep_row(const int32_t* perm, int k, int n_rows) {
-  const int r = perm[k];
-  return r < 0 ? 0 : (r >= n_rows ? n_rows - 1 : r);
+// rows perm[b .. b + n) of group g, clamped to the n_rows entries of perm: a segment without a cap
+__device__ __forceinline__ SegSpan prep_range(const int32_t* offs, int g, int n_rows) {
+  return seg_span(offs[g], offs[g + 1], n_rows);
 }
 
 template <typename T> struct PrepPair;
@@ -92,7 +85,7 @@ struct PrepLane {
 // chains then read lane by lane with readlane -- no scalar load sits between two batches of pixel loads.
 __device__ __forceinline__ int prep_rows(const int32_t* perm, int k0, int e, int lane, int n_rows) {
   const int k = k0 + lane;
-  return k < e ? prep_row(perm, k, n_rows) : 0;
+  return k < e ? seg_row(perm, k, n_rows) : 0;
 }
 
 // The sums over the members perm[b .. e), in that order from +0.0, of x (SQ = false) or of (x - m)^2
@@ -192,7 +185,7 @@ __global__ void __launch_bounds__(256) diversity_small_kernel(const T* __restric
   const int unit = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
   if (unit >= a.G * a.tiles) return;                  // wave-uniform; the kernel has no barrier
   const int g = unit / a.tiles, t = unit - g * a.tiles;
-  const PrepRange r = prep_range(a.offs, g, a.n);
+  const SegSpan r = prep_range(a.offs, g, a.n);
   if (r.n > PREP_SPLIT_MIN) {
     if (t == 0 && lane == 0) a.list[atomicAdd(a.count, 1)] = g;   // at most one entry per group: < G
     return;
@@ -249,7 +242,7 @@ __global__ void __launch_bounds__(PREP_CHUNKS * 64) diversity_large_kernel(const
   for (int j = blockIdx.x / a.tiles; j < listed; j += cap) {      // block-uniform trip count
     int g = a.list[j];
     g = g < 0 ? 0 : (g >= a.G ? a.G - 1 : g);
-    const PrepRange r = prep_range(a.offs, g, a.n);
+    const SegSpan r = prep_range(a.offs, g, a.n);
     const int L = (r.n + PREP_CHUNKS - 1) / PREP_CHUNKS;
     const int lo = wid * L < r.n ? wid * L : r.n, hi = (wid + 1) * L < r.n ? (wid + 1) * L : r.n;
     const double dn = (double)r.n;

@@ -19,6 +19,7 @@
 // Reductions: per thread in index order, then block_sum_d: a fixed order, no atomics, bitwise
 // reproducible.
 #include "common.h"
+#include "segment.h"
 
 namespace {
 
@@ -33,43 +34,20 @@ struct WsArgs {
   int channels;
 };
 
-// one side of one segment: first position and length, clamped to the rows and to the cap
-struct WsSide { int b, n; };
-__device__ __forceinline__ WsSide ws_side(const int32_t* seg, int s, int rows, int cap) {
-  int b = seg[2 * s], e = seg[2 * s + 1];
-  b = b < 0 ? 0 : (b > rows ? rows : b);
-  e = e < b ? b : (e > rows ? rows : e);
-  const int n = e - b;
-  return {b, n < cap ? n : cap};
-}
-
 __device__ __forceinline__ int ws_pow2(int m) {       // next power of two, >= 2
   int p = 2;
   while (p < m) p <<= 1;
   return p;
 }
 
-__device__ __forceinline__ uint64_t ws_key(double x) {
-  const uint64_t b = (uint64_t)__double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ws_val(uint64_t k) {
-  const uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-
 // element i of problem (s, c): i < nu from u, i < nu + nv from v, else padding
-__device__ __forceinline__ void ws_fetch(const WsArgs& a, int c, WsSide su, WsSide sv, int i, uint64_t& key,
+__device__ __forceinline__ void ws_fetch(const WsArgs& a, int c, SegSpan su, SegSpan sv, int i, uint64_t& key,
                                          uint8_t& tag) {
   if (i < su.n) {
-    int r = a.u_idx ? a.u_idx[su.b + i] : su.b + i;
-    r = r < 0 ? 0 : (r >= a.u_rows ? a.u_rows - 1 : r);
-    key = ws_key(a.u[(int64_t)r * a.u_ld + c]);
+    key = f64_key(a.u[(int64_t)seg_row(a.u_idx, su.b + i, a.u_rows) * a.u_ld + c]);
     tag = 1;
   } else if (i < su.n + sv.n) {
-    int r = a.v_idx ? a.v_idx[sv.b + i - su.n] : sv.b + i - su.n;
-    r = r < 0 ? 0 : (r >= a.v_rows ? a.v_rows - 1 : r);
-    key = ws_key(a.v[(int64_t)r * a.v_ld + c]);
+    key = f64_key(a.v[(int64_t)seg_row(a.v_idx, sv.b + i - su.n, a.v_rows) * a.v_ld + c]);
     tag = 0;
   } else {
     key = WS_PAD;
@@ -122,7 +100,7 @@ __device__ __forceinline__ double ws_sum(const uint64_t* keys, const uint8_t* ta
     }
     if (live) {
       const int cu = base + pre + __popcll(bal & le), cv = k + 1 - cu;
-      const double d = ws_val(keys[k + 1]) - ws_val(keys[k]);
+      const double d = f64_unkey(keys[k + 1]) - f64_unkey(keys[k]);
       acc += fabs((double)cu / dnu - (double)cv / dnv) * d;
     }
     base += tot;
@@ -138,7 +116,7 @@ __global__ void __launch_bounds__(WS_THREADS) ws_lds_kernel(WsArgs a, double* __
   __shared__ int shi[WS_THREADS / 64];
   __shared__ double shd[WS_THREADS / 64];
   const int prob = blockIdx.x, s = prob / a.channels, c = prob - s * a.channels;
-  const WsSide su = ws_side(a.u_seg, s, a.u_rows, a.u_cap), sv = ws_side(a.v_seg, s, a.v_rows, a.v_cap);
+  const SegSpan su = seg_span(a.u_seg, s, a.u_rows, a.u_cap), sv = seg_span(a.v_seg, s, a.v_rows, a.v_cap);
   if (su.n == 0 || sv.n == 0) {                      // block-uniform
     if (threadIdx.x == 0) out[prob] = 0.0;
     return;
@@ -161,7 +139,7 @@ __global__ void __launch_bounds__(WS_THREADS) ws_tile_kernel(WsArgs a, int P, in
   __shared__ uint64_t sk[WS_TILE];
   __shared__ uint8_t st[WS_TILE];
   const int prob = blockIdx.y, s = prob / a.channels, c = prob - s * a.channels;
-  const WsSide su = ws_side(a.u_seg, s, a.u_rows, a.u_cap), sv = ws_side(a.v_seg, s, a.v_rows, a.v_cap);
+  const SegSpan su = seg_span(a.u_seg, s, a.u_rows, a.u_cap), sv = seg_span(a.v_seg, s, a.v_rows, a.v_cap);
   if (su.n == 0 || sv.n == 0) return;
   const int pm = ws_pow2(su.n + sv.n);               // <= P
   const int base = blockIdx.x * WS_TILE;
@@ -184,7 +162,7 @@ __global__ void __launch_bounds__(WS_THREADS) ws_tile_kernel(WsArgs a, int P, in
 __global__ void __launch_bounds__(WS_THREADS) ws_global_stage_kernel(WsArgs a, int P, int k, int j, uint64_t* wk,
                                                                      uint8_t* wt) {
   const int prob = blockIdx.y, s = prob / a.channels;
-  const WsSide su = ws_side(a.u_seg, s, a.u_rows, a.u_cap), sv = ws_side(a.v_seg, s, a.v_rows, a.v_cap);
+  const SegSpan su = seg_span(a.u_seg, s, a.u_rows, a.u_cap), sv = seg_span(a.v_seg, s, a.v_rows, a.v_cap);
   if (su.n == 0 || sv.n == 0) return;
   const int pm = ws_pow2(su.n + sv.n);
   const int t = blockIdx.x * WS_THREADS + threadIdx.x;
@@ -206,7 +184,7 @@ __global__ void __launch_bounds__(WS_THREADS) ws_sum_kernel(WsArgs a, int P, con
   __shared__ int shi[WS_THREADS / 64];
   __shared__ double shd[WS_THREADS / 64];
   const int prob = blockIdx.x, s = prob / a.channels;
-  const WsSide su = ws_side(a.u_seg, s, a.u_rows, a.u_cap), sv = ws_side(a.v_seg, s, a.v_rows, a.v_cap);
+  const SegSpan su = seg_span(a.u_seg, s, a.u_rows, a.u_cap), sv = seg_span(a.v_seg, s, a.v_rows, a.v_cap);
   if (su.n == 0 || sv.n == 0) {
     if (threadIdx.x == 0) out[prob] = 0.0;
     return;

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from ..segments import check_segments, expert_segments, is_f64, ld, unit_stride_matrix, work_buffer
 
 
 def _values(values, device=None) -> torch.Tensor:
@@ -38,22 +39,7 @@ def _values(values, device=None) -> torch.Tensor:
         t = t.double()
     if not t.is_cuda:
         t = t.to(torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device()))
-    if t.shape[0] > 1 and (t.stride(0) < t.shape[1] or (t.shape[1] > 1 and t.stride(1) != 1)):
-        t = t.contiguous()
-    return t
-
-
-def _ld(x) -> int:
-    return int(x.stride(0)) if x.shape[0] > 1 else max(int(x.stride(0)), int(x.shape[1]))
-
-
-def _check_segments(x, seg, idx):
-    if seg.dtype != torch.int32 or seg.device != x.device or seg.numel() % 2 or not seg.is_contiguous():
-        raise ValueError("seg must be a contiguous device int32 [n_seg, 2] tensor")
-    if idx is not None and (idx.dtype != torch.int32 or idx.device != x.device or not idx.is_contiguous()
-                            or idx.numel() != x.shape[0]):
-        raise ValueError(f"idx must be a contiguous device int32 [{x.shape[0]}] tensor")
-    return seg.numel() // 2
+    return unit_stride_matrix(t)
 
 
 def segment_histogram_raw(x, seg, idx=None, seg_cap=None, bins=50, right=False, edges=None, cols=None):
@@ -66,7 +52,7 @@ def segment_histogram_raw(x, seg, idx=None, seg_cap=None, bins=50, right=False, 
     N = int(x.shape[0])
     cols = int(x.shape[1]) if cols is None else int(cols)
     bins = int(bins)
-    S = _check_segments(x, seg, idx)
+    S = check_segments(x, seg, idx)
     counts = torch.zeros(S, cols, max(bins, 0), dtype=torch.int32, device=x.device)
     outside = torch.zeros(S, cols, dtype=torch.int32, device=x.device)
     edges_out = torch.zeros(cols, max(bins, 0) + 1, dtype=torch.float64, device=x.device)
@@ -78,8 +64,8 @@ def segment_histogram_raw(x, seg, idx=None, seg_cap=None, bins=50, right=False, 
             edges_out.copy_(edges)
     with torch.cuda.device(x.device):
         need = hip.segment_histogram_workspace(cols, bins)
-        work = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
-        hip.call("es_segment_histogram", hip.ptr(x), 1 if x.dtype == torch.float64 else 0, _ld(x), N, cols,
+        work = work_buffer(need, x.device)
+        hip.call("es_segment_histogram", hip.ptr(x), is_f64(x), ld(x), N, cols,
                  hip.ptr(idx), hip.ptr(seg), S, int(seg_cap) if seg_cap is not None else max(N, 1), bins,
                  1 if right else 0, hip.ptr(edges), hip.ptr(edges_out), hip.ptr(counts), hip.ptr(outside),
                  hip.ptr(work), need, hip.stream_ptr())
@@ -96,7 +82,7 @@ def segment_kde_raw(x, seg, idx=None, seg_cap=None, points=100, grid=None, min_s
     N = int(x.shape[0])
     cols = int(x.shape[1]) if cols is None else int(cols)
     points = int(points)
-    S = _check_segments(x, seg, idx)
+    S = check_segments(x, seg, idx)
     dev = x.device
     density = torch.full((S, cols, max(points, 0)), float("nan"), dtype=torch.float64, device=dev)
     bw = torch.zeros(S, cols, dtype=torch.float64, device=dev)
@@ -112,32 +98,11 @@ def segment_kde_raw(x, seg, idx=None, seg_cap=None, points=100, grid=None, min_s
     cap = int(seg_cap) if seg_cap is not None else max(N, 1)
     with torch.cuda.device(dev):
         need = hip.segment_kde_workspace(S, cols, points, min(cap, max(N, 1))) if S > 0 else 0
-        work = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
-        hip.call("es_segment_kde", hip.ptr(x), 1 if x.dtype == torch.float64 else 0, _ld(x), N, cols, hip.ptr(idx),
+        work = work_buffer(need, dev)
+        hip.call("es_segment_kde", hip.ptr(x), is_f64(x), ld(x), N, cols, hip.ptr(idx),
                  hip.ptr(seg), S, cap, points, hip.ptr(grid), int(min_samples), float(std_eps), hip.ptr(grid_out),
                  hip.ptr(density), hip.ptr(bw), hip.ptr(valid), hip.ptr(sd), hip.ptr(work), need, hip.stream_ptr())
     return {"density": density, "grid": grid_out, "bw": bw, "sd": sd, "valid": valid}
-
-
-def expert_segments(expert, n_experts: int, n_rows: int, device):
-    """(seg [E, 2] int32, perm int32 [N] or None, offs int32 [E + 1] or None) on the device: expert e's samples
-    are perm[seg[e, 0] .. seg[e, 1]), in batch order -- one es_router_dispatch, as ws_across_experts_device
-    does it.  expert None: one segment over all rows, no perm."""
-    E, N = int(n_experts), int(n_rows)
-    if expert is None:
-        if E != 1:
-            raise ValueError(f"n_experts = {E} needs an expert vector")
-        return torch.tensor([[0, N]], dtype=torch.int32, device=device), None, None
-    if tuple(expert.shape) != (N,):
-        raise ValueError(f"expert must be [{N}], got {tuple(expert.shape)}")
-    expert = expert.to(device=device, dtype=torch.int32).contiguous()
-    perm = torch.empty(N, dtype=torch.int32, device=device)
-    offs = torch.zeros(E + 1, dtype=torch.int32, device=device)
-    if N > 0:
-        with torch.cuda.device(device):
-            hip.call("es_router_dispatch", hip.ptr(expert), N, E, hip.ptr(perm), hip.ptr(offs), hip.stream_ptr())
-    seg = torch.stack([offs[:-1], offs[1:]], dim=1).contiguous()
-    return seg, perm, offs
 
 
 def segment_histogram(values, expert=None, n_experts=1, bins=50, right=False, edges=None):
@@ -146,7 +111,7 @@ def segment_histogram(values, expert=None, n_experts=1, bins=50, right=False, ed
     right=True pd.cut(include_lowest=True)'s; edges None: np.linspace(min, max, bins + 1) per column over all
     N samples.  expert [N] int32 (None: one segment over all samples)."""
     x = _values(values)
-    seg, perm, _ = expert_segments(expert, n_experts, x.shape[0], x.device)
+    perm, seg, _ = expert_segments(expert, n_experts, x.shape[0], x.device)
     return segment_histogram_raw(x, seg, perm, None, bins, right, edges)
 
 
@@ -155,7 +120,7 @@ def segment_kde(values, expert=None, n_experts=1, points=100, grid=None, min_sam
     `points` values (grid None: np.linspace(min, max, points) per column over all N samples): the dict of
     segment_kde_raw, device tensors."""
     x = _values(values)
-    seg, perm, _ = expert_segments(expert, n_experts, x.shape[0], x.device)
+    perm, seg, _ = expert_segments(expert, n_experts, x.shape[0], x.device)
     return segment_kde_raw(x, seg, perm, None, points, grid, min_samples, std_eps)
 
 
@@ -195,7 +160,7 @@ def expert_diagnostics(cond, expert, n_experts, photon_sum, names=None, bins=50,
         raise ValueError(f"expert_diagnostics: photon_sum {tuple(ps.shape)} for {N} conditions")
     if expert is None:
         expert = torch.zeros(N, dtype=torch.int32, device=dev)
-    seg, perm, offs = expert_segments(expert, E, N, dev)
+    perm, seg, offs = expert_segments(expert, E, N, dev)
     ps_hist, ps_edges, _ = segment_histogram_raw(ps, seg, perm, None, bins, False)
     c_hist, c_edges, _ = segment_histogram_raw(c, seg, perm, None, bins, True)
     kde = segment_kde_raw(c, seg, perm, None, points, cols=C - 1)

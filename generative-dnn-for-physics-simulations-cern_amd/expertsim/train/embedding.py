@@ -19,14 +19,11 @@ import numpy as np
 import torch
 
 from .. import hip
-from .diagnostics import _ld, _values
+from ..segments import is_f64, ld, work_buffer
+from .diagnostics import _values
 
 EMBEDDING_KEYS = ("embed_rows", "embed_expert", "pca", "pca_components", "pca_explained_variance",
                   "pca_explained_variance_ratio", "tsne", "tsne_kl")
-
-
-def _work(nbytes, dev):
-    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)
 
 
 def pca_project(values, n_components=2):
@@ -42,8 +39,8 @@ def pca_project(values, n_components=2):
            "explained_variance_ratio": torch.zeros(max(k, 0), **f64), "mean": torch.zeros(C, **f64)}
     with torch.cuda.device(dev):
         need = hip.pca_project_workspace(C)
-        work = _work(need, dev)
-        hip.call("es_pca_project", hip.ptr(x), 1 if x.dtype == torch.float64 else 0, _ld(x), N, C, k,
+        work = work_buffer(need, dev)
+        hip.call("es_pca_project", hip.ptr(x), is_f64(x), ld(x), N, C, k,
                  hip.ptr(out["scores"]), hip.ptr(out["components"]), hip.ptr(out["explained_variance"]),
                  hip.ptr(out["explained_variance_ratio"]), hip.ptr(out["mean"]), hip.ptr(work), need,
                  hip.stream_ptr())
@@ -66,7 +63,7 @@ def tsne_affinities(values, perplexity=30.0):
            "dmin": torch.zeros(N, dtype=torch.float32, device=dev),
            "steps": torch.zeros(N, dtype=torch.int32, device=dev)}
     with torch.cuda.device(dev):
-        hip.call("es_tsne_affinities", hip.ptr(x), _ld(x), N, C, float(perplexity), hip.ptr(out["beta"]),
+        hip.call("es_tsne_affinities", hip.ptr(x), ld(x), N, C, float(perplexity), hip.ptr(out["beta"]),
                  hip.ptr(out["log_s"]), hip.ptr(out["dmin"]), hip.ptr(out["steps"]), hip.stream_ptr())
     return out
 
@@ -86,8 +83,8 @@ def tsne_gradient(values, aff, y, exaggeration=1.0):
     z_kl = torch.zeros(2, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         need = hip.tsne_workspace(N)
-        work = _work(need, dev)
-        hip.call("es_tsne_gradient", hip.ptr(x), _ld(x), N, C, hip.ptr(aff["beta"]), hip.ptr(aff["log_s"]),
+        work = work_buffer(need, dev)
+        hip.call("es_tsne_gradient", hip.ptr(x), ld(x), N, C, hip.ptr(aff["beta"]), hip.ptr(aff["log_s"]),
                  hip.ptr(aff["dmin"]), hip.ptr(y), float(exaggeration), hip.ptr(g), hip.ptr(z_kl), hip.ptr(work), need,
                  hip.stream_ptr())
     return g, z_kl
@@ -116,8 +113,8 @@ def tsne_run(values, aff, y, upd, gains, n_iter, iter0=0, log=None, exaggeration
         log = torch.cat([log, torch.full((rows - log.shape[0], 2), float("nan"), dtype=torch.float64, device=dev)])
     with torch.cuda.device(dev):
         need = hip.tsne_workspace(N)
-        work = _work(need, dev)
-        hip.call("es_tsne_run", hip.ptr(x), _ld(x), N, C, hip.ptr(aff["beta"]), hip.ptr(aff["log_s"]),
+        work = work_buffer(need, dev)
+        hip.call("es_tsne_run", hip.ptr(x), ld(x), N, C, hip.ptr(aff["beta"]), hip.ptr(aff["log_s"]),
                  hip.ptr(aff["dmin"]), hip.ptr(y), hip.ptr(upd), hip.ptr(gains), n_iter, iter0, float(exaggeration),
                  int(exaggeration_iters), float(momentum0), float(momentum1), lr, float(min_gain), check_every,
                  hip.ptr(log), int(log.shape[0]), hip.ptr(work), need, hip.stream_ptr())

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from ..segments import check_segments, expert_segments, ld, unit_stride_matrix, work_buffer
 
 METRICS = ("precision", "recall", "density", "coverage")
 
@@ -38,19 +39,12 @@ def _matrix(x) -> torch.Tensor:
         t = t.reshape(t.shape[0], -1)
     if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
         raise ValueError(f"x must be [rows, cols] with at least one of each, got {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.shape[0] > 1 and (t.stride(0) < t.shape[1] or (t.shape[1] > 1 and t.stride(1) != 1)):
-        t = t.contiguous()
-    return t
-
-
-def _ld(x) -> int:
-    return int(x.stride(0)) if x.shape[0] > 1 else max(int(x.stride(0)), int(x.shape[1]))
+    return unit_stride_matrix(t if t.dtype == torch.float32 else t.float())
 
 
 def _segments(x, idx, seg, cap):
-    """(idx, seg [n_seg, 2], n_seg, cap) as device int32 tensors; the default is one segment of all rows."""
+    """(idx, seg [n_seg, 2], n_seg, cap) as device int32 tensors; the default is one segment of all rows, and an
+    idx longer than the rows is cut to them (no position past the rows is read)."""
     dev, rows = x.device, int(x.shape[0])
     if seg is None:
         seg = torch.tensor([[0, rows]], dtype=torch.int32, device=dev)
@@ -59,11 +53,8 @@ def _segments(x, idx, seg, cap):
         idx = torch.as_tensor(idx).to(device=dev, dtype=torch.int32).contiguous()
         if idx.dim() != 1 or idx.shape[0] < rows:
             raise ValueError(f"idx must have the {rows} entries of x's rows, got {tuple(idx.shape)}")
-    return idx, seg, int(seg.shape[0]), rows if cap is None else int(cap)
-
-
-def _work(nbytes, dev):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+        idx = idx[:rows]
+    return idx, seg, check_segments(x, seg, idx), rows if cap is None else int(cap)
 
 
 def knn_radius(x, k, idx=None, seg=None, cap=None, out=None) -> torch.Tensor:
@@ -75,10 +66,10 @@ def knn_radius(x, k, idx=None, seg=None, cap=None, out=None) -> torch.Tensor:
     rows, cols = int(x.shape[0]), int(x.shape[1])
     with torch.cuda.device(x.device):
         need = hip.knn_radius_workspace(n_seg, cap, k)
-        work = _work(need, x.device)
+        work = work_buffer(need, x.device)
         if out is None:
             out = torch.full((n_seg, max(cap, 0)), float("nan"), dtype=torch.float64, device=x.device)
-        hip.call("es_knn_radius", hip.ptr(x), _ld(x), rows, cols, hip.ptr(idx), hip.ptr(seg), n_seg, cap, int(k),
+        hip.call("es_knn_radius", hip.ptr(x), ld(x), rows, cols, hip.ptr(idx), hip.ptr(seg), n_seg, cap, int(k),
                  hip.ptr(out), hip.ptr(work), int(work.numel()) if need else 0, hip.stream_ptr())
     return out
 
@@ -111,9 +102,9 @@ def prdc_raw(real, fake, k, r_idx=None, r_seg=None, r_cap=None, f_idx=None, f_se
             r_hit = torch.full((n_seg, max(r_cap, 0)), -1, dtype=torch.int32, device=dev)
             r_min2 = torch.full((n_seg, max(r_cap, 0)), float("nan"), dtype=torch.float64, device=dev)
         need = hip.prdc_workspace(n_seg, r_cap, f_cap)
-        work = _work(need, dev)
-        hip.call("es_prdc_count", hip.ptr(real), _ld(real), int(real.shape[0]), hip.ptr(r_idx), hip.ptr(r_seg), r_cap,
-                 hip.ptr(fake), _ld(fake), int(fake.shape[0]), hip.ptr(f_idx), hip.ptr(f_seg), f_cap,
+        work = work_buffer(need, dev)
+        hip.call("es_prdc_count", hip.ptr(real), ld(real), int(real.shape[0]), hip.ptr(r_idx), hip.ptr(r_seg), r_cap,
+                 hip.ptr(fake), ld(fake), int(fake.shape[0]), hip.ptr(f_idx), hip.ptr(f_seg), f_cap,
                  int(real.shape[1]), n_seg, int(k), hip.ptr(r_radius2), hip.ptr(f_radius2), hip.ptr(f_count),
                  hip.ptr(r_hit), hip.ptr(r_min2), hip.ptr(totals), hip.ptr(work), int(work.numel()) if need else 0,
                  hip.stream_ptr())
@@ -136,24 +127,6 @@ def metrics_from_totals(totals, k) -> np.ndarray:
     return out
 
 
-def expert_segments(expert, n_experts):
-    """(perm [N] int32, seg [E + 1, 2] int32) on the device from one es_router_dispatch: segment 0 is (0, N), segment
-    1 + e is (offs[e], offs[e + 1]) -- train.utils.ws_across_experts_device's segments."""
-    hip.require_device(expert)
-    dev, E, N = expert.device, int(n_experts), int(expert.shape[0])
-    expert = expert.to(dtype=torch.int32).contiguous()
-    perm = torch.empty(N, dtype=torch.int32, device=dev)
-    offs = torch.empty(E + 1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        hip.call("es_router_dispatch", hip.ptr(expert), N, E, hip.ptr(perm), hip.ptr(offs), hip.stream_ptr())
-    seg = torch.empty(E + 1, 2, dtype=torch.int32, device=dev)
-    seg[0, 0] = 0
-    seg[0, 1] = N
-    seg[1:, 0] = offs[:-1]
-    seg[1:, 1] = offs[1:]
-    return perm, seg
-
-
 def prdc_device(real, fake, k=5, expert=None, n_experts=1, per_row=False):
     """The device half of `prdc`: prdc_raw's dict over the segments of `expert` (no host synchronisation)."""
     real, fake = _matrix(real), _matrix(fake)
@@ -163,7 +136,7 @@ def prdc_device(real, fake, k=5, expert=None, n_experts=1, per_row=False):
         raise ValueError(f"with an expert vector real, fake and expert are aligned: {real.shape[0]}, {fake.shape[0]}, "
                          f"{tuple(expert.shape)}")
     N = int(real.shape[0])
-    perm, seg = expert_segments(expert.to(real.device), n_experts)
+    perm, seg, _ = expert_segments(expert, n_experts, N, real.device, joint=True)
     raw = prdc_raw(real, fake, k, r_idx=perm, r_seg=seg, r_cap=N, f_idx=perm, f_seg=seg, f_cap=N, per_row=per_row)
     raw.update(perm=perm, seg=seg)
     return raw

@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from ..segments import WORK_MIN, check_segments, expert_segments
 
 
 def get_channel_masks(input_array: np.ndarray):
@@ -285,7 +286,7 @@ _WS_SEG = {}       # (device, rows) -> the default one-segment bounds [[0, rows]
 def _ws_workspace(nbytes: int, device) -> torch.Tensor:
     w = _WS_WORK.get(device)
     if w is None or w.numel() < nbytes:
-        w = _WS_WORK[device] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+        w = _WS_WORK[device] = torch.empty(max(nbytes, WORK_MIN), dtype=torch.uint8, device=device)
     return w
 
 
@@ -300,11 +301,7 @@ def _ws_side(name, t, seg, idx, cap):
         seg = _WS_SEG.get(key)
         if seg is None:
             seg = _WS_SEG[key] = torch.tensor([[0, rows]], dtype=torch.int32, device=t.device)
-    if seg.dtype != torch.int32 or seg.device != t.device or seg.numel() % 2 or not seg.is_contiguous():
-        raise ValueError(f"wasserstein_1d_device: {name}_seg must be a contiguous device int32 [n_seg, 2] tensor")
-    if idx is not None and (idx.dtype != torch.int32 or idx.device != t.device or not idx.is_contiguous()
-                            or idx.numel() != rows):
-        raise ValueError(f"wasserstein_1d_device: {name}_idx must be a contiguous device int32 [{rows}] tensor")
+    check_segments(t, seg, idx, f"wasserstein_1d_device: {name}_")
     return rows, seg, idx, rows if cap is None else int(cap)
 
 
@@ -352,16 +349,7 @@ def ws_across_experts_device(ch_org, ch_gen, expert, n_experts) -> torch.Tensor:
                          f"expert {tuple(expert.shape)}")
     if R * N > np.iinfo(np.int32).max:
         raise ValueError(f"ws_across_experts_device: {R} x {N} rows exceed int32")
-    expert = expert.to(device=dev, dtype=torch.int32).contiguous()
-    perm = torch.empty(N, dtype=torch.int32, device=dev)
-    offs = torch.empty(E + 1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        hip.call("es_router_dispatch", hip.ptr(expert), N, E, hip.ptr(perm), hip.ptr(offs), hip.stream_ptr())
-    seg = torch.empty(E + 1, 2, dtype=torch.int32, device=dev)
-    seg[0, 0] = 0
-    seg[0, 1] = N
-    seg[1:, 0] = offs[:-1]
-    seg[1:, 1] = offs[1:]
+    perm, seg, _ = expert_segments(expert, E, N, dev, joint=True)
     shift = torch.arange(R, dtype=torch.int32, device=dev) * N
     u_seg = seg.repeat(R, 1)
     v_seg = (seg[None] + shift[:, None, None]).reshape(R * (E + 1), 2).contiguous()

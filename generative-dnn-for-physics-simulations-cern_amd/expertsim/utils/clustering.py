@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from ..segments import is_f64, ld, unit_stride_matrix, work_buffer
 
 
 def _matrix(x, device=None) -> torch.Tensor:
@@ -40,17 +41,7 @@ def _matrix(x, device=None) -> torch.Tensor:
         t = t.double()
     if not t.is_cuda:
         t = t.to(torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device()))
-    if t.shape[0] > 1 and (t.stride(0) < t.shape[1] or (t.shape[1] > 1 and t.stride(1) != 1)):
-        t = t.contiguous()
-    return t
-
-
-def _ld(x) -> int:
-    return int(x.stride(0)) if x.shape[0] > 1 else max(int(x.stride(0)), int(x.shape[1]))
-
-
-def _work(nbytes, dev):
-    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)
+    return unit_stride_matrix(t)
 
 
 def _check(x, K):
@@ -68,9 +59,9 @@ class _Lloyd:
         self.x = x
         self.rows, self.cols, self.K = _check(x, K)
         dev = x.device
-        self.f64 = 1 if x.dtype == torch.float64 else 0
+        self.f64 = is_f64(x)
         self.need = hip.kmeans_workspace(self.rows, self.cols, self.K)
-        self.work = _work(self.need, dev)
+        self.work = work_buffer(self.need, dev)
         self.labels = [torch.zeros(self.rows, dtype=torch.int32, device=dev) for _ in range(2)]
         self.dist = torch.zeros(self.rows, dtype=torch.float64, device=dev)
         # [changed (int64 bits), inertia, shift, threshold]: what the host reads once per iteration
@@ -80,12 +71,12 @@ class _Lloyd:
         return C.c_void_p(self.stat.data_ptr() + 8 * i)
 
     def assign(self, centres, label, label_old):
-        hip.call("es_kmeans_assign", hip.ptr(self.x), self.f64, _ld(self.x), self.rows, self.cols, hip.ptr(centres),
+        hip.call("es_kmeans_assign", hip.ptr(self.x), self.f64, ld(self.x), self.rows, self.cols, hip.ptr(centres),
                  self.K, hip.ptr(label_old), hip.ptr(label), hip.ptr(self.dist), self._stat(0), self._stat(1),
                  hip.ptr(self.work), self.need, hip.stream_ptr())
 
     def update(self, label, centres_old, centres_new):
-        hip.call("es_kmeans_update", hip.ptr(self.x), self.f64, _ld(self.x), self.rows, self.cols, hip.ptr(label),
+        hip.call("es_kmeans_update", hip.ptr(self.x), self.f64, ld(self.x), self.rows, self.cols, hip.ptr(label),
                  hip.ptr(self.dist), hip.ptr(centres_old), self.K, hip.ptr(centres_new), self._stat(2),
                  hip.ptr(self.work), self.need, hip.stream_ptr())
 
@@ -164,8 +155,8 @@ def kmeans_plusplus_raw(x, K, draws):
     index = torch.zeros(K, dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
         need = hip.kmeans_plusplus_workspace(rows, cols, K)
-        work = _work(need, x.device)
-        hip.call("es_kmeans_plusplus", hip.ptr(x), 1 if x.dtype == torch.float64 else 0, _ld(x), rows, cols, K,
+        work = work_buffer(need, x.device)
+        hip.call("es_kmeans_plusplus", hip.ptr(x), is_f64(x), ld(x), rows, cols, K,
                  hip.ptr(u), int(u.shape[1]), hip.ptr(centres), hip.ptr(index), hip.ptr(work), need,
                  hip.stream_ptr())
     return centres, index

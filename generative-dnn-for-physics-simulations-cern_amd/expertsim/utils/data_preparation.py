@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from ..segments import is_f64, work_buffer
 from .data_transformations import COND_COLUMNS, ZDCType, _photon_sum_column
 
 logger = logging.getLogger(__name__)
@@ -124,8 +125,8 @@ def diversity_raw(x, perm, offs, n_groups: int, return_maps: bool = False):
     view = _view(x)
     with torch.cuda.device(x.device):
         need = int(hip.lib().es_group_diversity_workspace(G, H, W))
-        work = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
-        hip.call("es_group_diversity", C.byref(view), 1 if x.dtype == torch.float64 else 0, hip.ptr(x),
+        work = work_buffer(need, x.device)
+        hip.call("es_group_diversity", C.byref(view), is_f64(x), hip.ptr(x),
                  hip.ptr(perm), hip.ptr(offs), G, hip.ptr(group_sum), hip.ptr(pix_var), hip.ptr(work), need,
                  hip.stream_ptr())
     return group_sum, pix_var
@@ -169,7 +170,7 @@ def photon_sums_and_peaks(images, device=None, check: bool = True):
         return s, peak
     view = _view(x)
     with torch.cuda.device(x.device):
-        hip.call("es_image_sum_peak", C.byref(view), 1 if x.dtype == torch.float64 else 0, hip.ptr(x), hip.ptr(s),
+        hip.call("es_image_sum_peak", C.byref(view), is_f64(x), hip.ptr(x), hip.ptr(s),
                  hip.ptr(peak), hip.stream_ptr())
     if check and not bool(torch.isfinite(s).all()):
         raise ValueError(f"non-finite pixel in image {_first_bad_image(x)}")

@@ -26,6 +26,7 @@ import os
 import numpy as np
 
 from golden_utils import GOLDEN_DIR
+from segment_refs import members
 
 SPLIT_MIN = 256          # ES_PREP_SPLIT_MIN
 CHUNKS = 16              # ES_PREP_CHUNKS
@@ -96,13 +97,11 @@ def group_diversity_ref(x, perm, offs):
     perm, offs = np.asarray(perm), np.asarray(offs)
     G = len(offs) - 1
     pix_var = np.zeros((G, flat.shape[1]), dtype=np.float64)
-    for g in range(G):
-        b = min(max(int(offs[g]), 0), N)
-        e = min(max(int(offs[g + 1]), b), N)
-        if e == b:
+    for g, m in enumerate(members(N, perm, np.stack([offs[:-1], offs[1:]], axis=1))):
+        if len(m) == 0:
             continue
-        rows = flat[np.clip(perm[b:e], 0, N - 1)]
-        n = np.float64(e - b)
+        rows = flat[m]
+        n = np.float64(len(m))
         m = _member_sum(rows) / n
         pix_var[g] = _member_sum(rows, m) / n
     return tile_sum(np.sqrt(pix_var)), pix_var

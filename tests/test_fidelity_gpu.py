@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import prdc_refs as R
+import segment_refs as S
 from conftest import REPO
 
 pytestmark = pytest.mark.gpu
@@ -26,17 +27,6 @@ DEV = "cuda"
 
 def _bits(a):
     return np.ascontiguousarray(a).view(np.int64)
-
-
-def _host_members(rows, idx, seg, cap):
-    """Row indices of every segment as the kernels clamp them."""
-    out = []
-    for b, e in np.asarray(seg).reshape(-1, 2):
-        b = min(max(int(b), 0), rows)
-        e = min(max(int(e), b), rows)
-        m = np.arange(b, min(e, b + cap))
-        out.append(np.clip(np.asarray(idx)[m], 0, rows - 1) if idx is not None else m)
-    return out
 
 
 def _check_against_restatement(real, fake, k, r_idx=None, r_seg=None, f_idx=None, f_seg=None, real_dev=None,
@@ -53,7 +43,7 @@ def _check_against_restatement(real, fake, k, r_idx=None, r_seg=None, f_idx=None
                    f_idx=None if f_idx is None else torch.from_numpy(f_idx).to(DEV),
                    f_seg=torch.from_numpy(f_seg.astype(np.int32)).to(DEV), f_cap=n_f)
     got = {key: v.cpu().numpy() for key, v in raw.items()}
-    m_r, m_f = _host_members(n_r, r_idx, r_seg, n_r), _host_members(n_f, f_idx, f_seg, n_f)
+    m_r, m_f = S.members(n_r, r_idx, r_seg, n_r), S.members(n_f, f_idx, f_seg, n_f)
     for s, (ir, jf) in enumerate(zip(m_r, m_f)):
         ref = R.segment(real[ir], fake[jf], k)
         L_r, L_f = len(ir), len(jf)
@@ -82,11 +72,14 @@ def golden():
 
 @pytest.mark.parametrize("arch", list(R.ARCHS))
 def test_record(golden, arch):
-    from expertsim.train.fidelity import expert_segments, prdc, prdc_raw
+    from expertsim.segments import expert_segments
+    from expertsim.train.fidelity import prdc, prdc_raw
     real, fake = golden[f"{arch}_real"], golden[f"{arch}_fake"]
     rd, fd = torch.from_numpy(real).to(DEV), torch.from_numpy(fake).to(DEV)
-    r_perm, r_seg = expert_segments(torch.from_numpy(golden[f"{arch}_expert_r"]).to(DEV), R.N_EXPERTS)
-    f_perm, f_seg = expert_segments(torch.from_numpy(golden[f"{arch}_expert_f"]).to(DEV), R.N_EXPERTS)
+    r_perm, r_seg, _ = expert_segments(torch.from_numpy(golden[f"{arch}_expert_r"]), R.N_EXPERTS, len(real), rd.device,
+                                       joint=True)
+    f_perm, f_seg, _ = expert_segments(torch.from_numpy(golden[f"{arch}_expert_f"]), R.N_EXPERTS, len(fake), fd.device,
+                                       joint=True)
     m_r = R.members(golden[f"{arch}_expert_r"], R.N_EXPERTS)
     m_f = R.members(golden[f"{arch}_expert_f"], R.N_EXPERTS)
     rp, rs_, fp, fs_ = (t.cpu().numpy() for t in (r_perm, r_seg, f_perm, f_seg))
@@ -190,7 +183,7 @@ def test_segments_of_a_router_dispatch():
     for e in range(3):
         assert sorted(perm[seg[1 + e, 0]:seg[1 + e, 1]].tolist()) == np.nonzero(expert == e)[0].tolist()
     _check_against_restatement(real, fake, k, r_idx=perm, r_seg=seg, f_idx=perm, f_seg=seg)
-    want = np.stack([R.segment(real[m], fake[m], k)["totals"] for m in _host_members(N, perm, seg, N)])
+    want = np.stack([R.segment(real[m], fake[m], k)["totals"] for m in S.members(N, perm, seg, N)])
     assert np.array_equal(raw["totals"].cpu().numpy(), want)
 
 

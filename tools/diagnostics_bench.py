@@ -149,7 +149,7 @@ def main():
            "device": torch.cuda.get_device_name(0), "warmup": 2, "reps": 7}
     res["expert_diagnostics_resident"] = limited(
         args.step_limit, timed, lambda: D.expert_diagnostics(cond_dev, expert, E, ps, bins=bins, points=points), sync)
-    seg, perm, _ = D.expert_segments(expert, E, N, dev)
+    perm, seg, _ = D.expert_segments(expert, E, N, dev)
     res["es_segment_histogram_events"] = limited(
         args.step_limit, by_events, lambda: D.segment_histogram_raw(cond_dev, seg, perm, None, bins, True))
     res["es_segment_kde_events"] = limited(

@@ -132,7 +132,7 @@ def main():
     experts = {1: torch.zeros(N, dtype=torch.int32, device=dev),
                4: torch.from_numpy(rs.randint(0, 4, N).astype(np.int32)).to(dev)}
     for E, expert in experts.items():
-        perm, seg = FD.expert_segments(expert, E)
+        perm, seg, _ = FD.expert_segments(expert, E, N, dev, joint=True)
         seg_h = seg.cpu().numpy().astype(np.int64)
         pairs = int(((seg_h[:, 1] - seg_h[:, 0]) ** 2).sum())          # both sides share the segments
         ops = 3.0 * pairs * cols
