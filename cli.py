@@ -8,10 +8,11 @@ The reference's CUDA_LAUNCH_BLOCKING / cudnn flags / anomaly detection (cli.py:2
 Simulation (conditions in, calorimeter images out; MoEWrapper.simulate) from a saved checkpoint:
     python cli.py -o model.architecture=neutron dataset.input_image_shape=[44,44] model.n_experts=3 \
         --simulate --checkpoint DIR [--checkpoint-epoch E] (--cond FILE.npy | --num-samples N) --out FILE.npz \
-        [--features] [--real FILE.npy [--prdc-k K]]
+        [--features] [--real FILE.npy [--prdc-k K] [--distances]]
 --real FILE.npy (real images [N,H,W] in the log1p domain, aligned with --cond) adds the sample-level precision /
 recall / density / coverage of the simulated images against them at K neighbours (default 5), jointly and per
-expert (expertsim/train/fidelity.py), as prdc_* entries of the .npz and on stdout.
+expert (expertsim/train/fidelity.py), as prdc_* entries of the .npz and on stdout.  --distances adds the Frechet
+and kernel distances of the ten shower observables (expertsim/train/distances.py) next to them as dist_* entries.
 
 Dataset preparation (raw responses + particle conditions in, the three pickles of dataset.source=pickle out;
 expertsim/utils/data_preparation.py) for the detector named by dataset.zdc_type:
@@ -62,6 +63,8 @@ def parse_args(args=None):
                    help=".npy real images [N,H,W] (log1p domain, aligned with --cond): also precision / recall / "
                         "density / coverage of the simulated images against them")
     g.add_argument("--prdc-k", type=int, default=5, help="neighbours of the --real metrics")
+    g.add_argument("--distances", action="store_true",
+                   help="with --real: also the Frechet and kernel distances of the ten shower observables (dist_*)")
     x = p.add_argument_group("expert diagnostics (instead of training)")
     x.add_argument("--diagnose", action="store_true",
                    help="per-expert histograms and KDEs for --conditions FILE from --checkpoint DIR, written to --out")
@@ -150,6 +153,17 @@ def simulate(args):
                 logger.info("prdc_%s = %.6f", name, v)
         extra["prdc_totals"] = m["totals"].cpu().numpy()
         extra["prdc_k"] = np.int64(args.prdc_k)
+        if args.distances:
+            from expertsim.train import distances as dist
+            feat = res["features"] if args.features else None
+            obs_real = dist.observables(torch.from_numpy(real).to(device), log_domain=True)
+            obs_gen = dist.observables(res["images"], log_domain=False, sums=res["sums"], features=feat)
+            obs_real, obs_gen, _ = dist.normalise(obs_real, obs_gen)
+            for name, v in dist.distances(obs_real, obs_gen, res["expert"], moe.n_experts).items():
+                extra[f"dist_{name}"] = np.float64(v)
+                logger.info("dist_%s = %.6g", name, v)
+    elif args.distances:
+        raise SystemExit("--distances needs --real FILE.npy")
     np.savez(args.out, images=res["images"].cpu().numpy(), expert=res["expert"].cpu().numpy(),
              sums=res["sums"].cpu().numpy(), cond=cond, **extra)
     logger.info("Simulated %d images (epoch %d checkpoint) -> %s", cond.shape[0], epoch, args.out)

@@ -233,6 +233,12 @@ _SIGS = {
     "es_knn_radius": (C.c_int, [P, I64, C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, P, C.c_size_t, P]),
     "es_prdc_count": (C.c_int, [P, I64, C.c_int, P, P, C.c_int, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int,
                                 C.c_int, P, P, P, P, P, P, P, C.c_size_t, P]),
+    "es_segment_moments_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "es_mmd_poly_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "es_segment_moments": (C.c_int, [P, C.c_int, I64, C.c_int, C.c_int, P, P, C.c_int, P, P, P, P, C.c_size_t, P]),
+    "es_frechet": (C.c_int, [P, P, P, P, C.c_int, C.c_int, P, P]),
+    "es_mmd_poly": (C.c_int, [P, I64, C.c_int, P, P, C.c_int, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int,
+                              C.c_int, C.c_double, C.c_double, P, P, P, C.c_size_t, P]),
 }
 
 # es_group_diversity's split of a large group (ES_PREP_SPLIT_MIN / ES_PREP_CHUNKS of include/expertsim_hip.h)
@@ -278,6 +284,24 @@ def knn_radius_workspace(n_seg: int, cap: int, k: int) -> int:
 def prdc_workspace(n_seg: int, r_cap: int, f_cap: int) -> int:
     """Bytes of es_prdc_count's workspace (0: outside the limits)."""
     return int(lib().es_prdc_workspace(int(n_seg), int(r_cap), int(f_cap)))
+
+
+# distribution distances (ES_DIST_* / ES_MOMENTS_* / ES_MMD_* of include/expertsim_hip.h)
+DIST_MAX_ROWS = 1 << 20
+DIST_MAX_SEG = 1024
+MOMENTS_MAX_COLS = 32
+MMD_MAX_COLS = 64
+MMD_MAX_DEGREE = 8
+
+
+def segment_moments_workspace(n_seg: int, cols: int) -> int:
+    """Bytes of es_segment_moments's workspace (0: outside the limits)."""
+    return int(lib().es_segment_moments_workspace(int(n_seg), int(cols)))
+
+
+def mmd_poly_workspace(n_seg: int, r_cap: int, f_cap: int) -> int:
+    """Bytes of es_mmd_poly's workspace (0: outside the limits)."""
+    return int(lib().es_mmd_poly_workspace(int(n_seg), int(r_cap), int(f_cap)))
 
 
 def kmeans_workspace(rows: int, cols: int, k: int) -> int:

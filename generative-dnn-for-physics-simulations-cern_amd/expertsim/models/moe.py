@@ -633,7 +633,8 @@ class MoEWrapper(nn.Module):
 
     @torch.no_grad()
     def evaluate_device(self, epoch, y_test, x_test, cfg, *, seed=0, sample_offset=0, routing="sample",
-                        fused=True, graph=True, details=False, features=False, prdc=False, prdc_k=5):
+                        fused=True, graph=True, details=False, features=False, prdc=False, prdc_k=5,
+                        distances=False):
         """The metrics of evaluate (same keys) from the simulate path, without a host round trip until
         the result: real sums by es_channel_sums, repetition j of the n_calc = min(epoch // 5 + 1, 5) by
         simulate(sums=True) -- j = 0 with simulate's own noise draw, j > 0 with es_randn_dev(seed + j) on
@@ -663,7 +664,17 @@ class MoEWrapper(nn.Module):
         prdc_coverage (joint) and prdc_<name>_<e> (expert e; NaN when either side has at most prdc_k rows
         there).  The integer totals cross to the host in a second small copy; details=True adds prdc_totals
         [E + 1, 8] and the radii.  These metrics depend on N and on prdc_k: compare equal settings only.  The
-        other keys keep their values bit for bit."""
+        other keys keep their values bit for bit.
+
+        distances=True adds the joint-distribution distances of train.distances over the ten observables
+        (OBSERVABLE_NAMES: the five channel sums next to the five shower shapes): the real side's table is
+        computed once, the generated side's is repetition 0's from the same simulate call (its sums, and its
+        features when features=True asked for them, else one image_features pass over its images), both are
+        divided by the joint real scale (train.distances.normalise) and `fpd` and `kpd` run over the segments of
+        the same expert vector: dist_fpd / dist_fpd_err / dist_fd_full / dist_kpd / dist_kpd_err / dist_mmd_full
+        (joint) and dist_<name>_<e> (expert e; NaN where the expert has too few rows).  One further small copy;
+        details=True adds dist_obs_real / dist_obs_gen [N, 10] (normalised), dist_scale [10], dist_fpd_table,
+        dist_fpd_frechet and dist_kpd_table.  The other keys keep their values bit for bit."""
         from ..train.utils import (FEATURE_NAMES, channel_sums, image_features, ws_across_experts_device,
                                    ws_feature_summary, ws_summary)
         dev = next(self.parameters()).device
@@ -700,6 +711,8 @@ class MoEWrapper(nn.Module):
                     expert = sim["expert"]
                 if prdc and j == 0:
                     gen_log = torch.log1p(sim["images"])
+                if distances and j == 0:
+                    gen_feat0 = feat_gen[0] if features else image_features(sim["images"])[0]
             ws = ws_across_experts_device(sums_real, sums_gen, expert, E)
             if features:
                 ws_feat = ws_across_experts_device(feat_real, feat_gen, expert, E)
@@ -727,6 +740,17 @@ class MoEWrapper(nn.Module):
             if details:
                 log.update(prdc_totals=raw["totals"], prdc_r_radius2=raw["r_radius2"],
                            prdc_f_radius2=raw["f_radius2"])
+        if distances:
+            from ..train import distances as dist
+            with torch.cuda.device(dev):
+                obs_real = dist.observables(x, sums=sums_real, features=feat_real if features else None)
+                obs_gen = dist.observables(None, sums=sums_gen[0], features=gen_feat0)
+                obs_real, obs_gen, scale = dist.normalise(obs_real, obs_gen)
+                d = dist.distances(obs_real, obs_gen, expert, E, details=bool(details))   # one small D2H copy
+            for name, v in d.items():
+                log[f"dist_{name}"] = v
+            if details:
+                log.update(dist_obs_real=obs_real, dist_obs_gen=obs_gen, dist_scale=scale)
         if details:
             log.update(sums_real=sums_real, sums_gen=sums_gen, expert=expert, ws=ws)
             if features:

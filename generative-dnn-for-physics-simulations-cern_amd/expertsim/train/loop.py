@@ -115,13 +115,21 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     evaluate_device(prdc=True, prdc_k=train.eval_prdc_k), each key averaged over the batches in which it is finite
     (an expert with at most k rows in a batch gives NaN there); NaN if it is finite in none.  These metrics
     depend on the batch size (the number of samples on each side) and on k, so runs are comparable only at equal
-    batch size and equal train.eval_prdc_k."""
+    batch size and equal train.eval_prdc_k.
+    train.eval_distances (with eval_on_device only): also the joint-distribution distances of
+    evaluate_device(distances=True) (train/distances.py: dist_fpd, dist_kpd and their companions, jointly and per
+    expert), each key averaged over the batches in which it is finite; NaN if it is finite in none.  Both
+    statistics depend on the number of samples in a batch: compare runs at equal batch size."""
     on_device = bool(cfg.train.get("eval_on_device", False))
     features = bool(cfg.train.get("eval_features", False))
     diagnostics = bool(cfg.train.get("eval_diagnostics", False))
     embedding = bool(cfg.train.get("eval_embedding", False))
     prdc = bool(cfg.train.get("eval_prdc", False))
     prdc_k = int(cfg.train.get("eval_prdc_k", 5))
+    distances = bool(cfg.train.get("eval_distances", False))
+    if distances and not on_device:
+        raise ValueError("train.eval_distances needs train.eval_on_device: the distribution distances exist on the "
+                         "device path only (MoEWrapper.evaluate_device)")
     if prdc and not on_device:
         raise ValueError("train.eval_prdc needs train.eval_on_device: the sample-level metrics exist on the device "
                          "path only (MoEWrapper.evaluate_device)")
@@ -146,6 +154,10 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
         from .fidelity import METRICS
         prdc_keys = [f"prdc_{name}" for name in METRICS]
         prdc_keys += [f"prdc_{name}_{i}" for i in range(moe.n_experts) for name in METRICS]
+    if distances:
+        from .distances import KEYS
+        prdc_keys += [f"dist_{name}" for name in KEYS]
+        prdc_keys += [f"dist_{name}_{i}" for i in range(moe.n_experts) for name in KEYS]
     acc: Dict[str, List[float]] = {k: [] for k in keys + prdc_keys}
     seen = 0                                   # test samples in earlier batches
     conds = []                                 # the batches' device conditions (eval_diagnostics)
@@ -156,6 +168,8 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
         if on_device:
             cond_dev = cond.to(device)
             extra = dict(prdc=True, prdc_k=prdc_k) if prdc else {}
+            if distances:
+                extra["distances"] = True
             m = moe.evaluate_device(epoch, cond_dev, real_images, cfg,
                                     seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=seen,
                                     features=features, **extra)

@@ -1119,6 +1119,72 @@ int es_prdc_count(const float* real, int64_t r_ld, int r_rows, const int32_t* r_
                   int64_t* totals /* [n_seg, 8] */, void* work, size_t work_bytes, es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Distances between the joint distributions of the shower observables: the Frechet distance between fitted
+ * Gaussians and the polynomial-kernel MMD of Kansal et al. 2023 ("Evaluating generative models in high energy
+ * physics") -- csrc/distance.hip.
+ * ---------------------------------------------------------------------------------------- */
+/* Every pointer is a DEVICE pointer; no host sync, everything runs on `stream`.  Outside the limits, with a NULL
+ * required pointer or too small a workspace: ES_ERR_ARG before any launch, and nothing is written.  Segments follow
+ * es_wasserstein_1d (see es_knn_radius above): rows idx[seg[2s] .. seg[2s+1]), idx NULL: the rows themselves, the
+ * bounds clamped to [0, rows], every row index to [0, rows); segments may overlap.  No float atomics: partial sums
+ * per chunk / tile go to the workspace and are added in a fixed order, so a rerun is bit-equal.  All arithmetic is
+ * fp64 (products and sums may be fused).
+ *
+ * es_segment_moments.  x [rows][ld], fp32 or fp64 (x_f64 != 0) with unit column stride, 1 <= cols <= ES_MOMENTS_MAX_COLS,
+ * cols <= ld, 1 <= rows <= ES_DIST_MAX_ROWS, 1 <= n_seg <= ES_DIST_MAX_SEG.  For segment s with the n members x_p:
+ *   count[s] (int32 [n_seg]) = n
+ *   mean[s][c] (fp64 [n_seg][cols]) = sum_p x_p[c] / n                                   (NaN when n == 0)
+ *   cov[s][i][j] (fp64 [n_seg][cols][cols]) = sum_p (x_p[i] - mean[i]) (x_p[j] - mean[j]) / (n - 1)   (NaN when n < 2)
+ * i.e. np.cov(rowvar=False): two passes, centred on the rounded mean.  The upper triangle i <= j is computed and
+ * mirrored, so cov[i][j] and cov[j][i] are the same bits.  Order of a sum: the members are cut into ES_MOMENTS_CHUNKS
+ * runs of max(64, ceil(n / ES_MOMENTS_CHUNKS)) consecutive members; within a run eight (mean) or one (cov) strided
+ * sequential chains, added in order; the runs in order.
+ * work: es_segment_moments_workspace(n_seg, cols) bytes (0: outside the limits): the runs' partial sums.
+ *
+ * es_frechet.  n problems (1 <= n <= ES_DIST_MAX_SEG, 1 <= cols <= ES_MOMENTS_MAX_COLS), problem i the moments
+ * mean_a[i][cols], cov_a[i][cols][cols], mean_b[i], cov_b[i] as es_segment_moments writes them (cov symmetric; the
+ * upper triangle is read).  out[i] (fp64 [n][4]) = { d2, |dmu|^2, tr A + tr B, tr (A B)^1/2 } with
+ *   d2 = |dmu|^2 + tr A + tr B - 2 tr (A B)^1/2,
+ *   tr (A B)^1/2 = sum_k sqrt(max(m_k, 0)), m_k the eigenvalues of the symmetric A^1/2 B A^1/2,
+ *   A^1/2 = V diag(sqrt(max(l_k, 0))) V^T from the eigendecomposition A = V diag(l) V^T.
+ * Both decompositions are cyclic Jacobi in fp64 (rotation skipped when |a_pq| <= 2^-56 sqrt(|a_pp a_qq|), at most 30
+ * sweeps), one workgroup per problem with the matrices in LDS.  A problem with a NaN anywhere in its moments gives
+ * NaN in all four outputs.
+ *
+ * es_mmd_poly.  real / fake fp32 [rows][ld] with their own ld / rows / idx / seg / cap (the host upper bound of a
+ * segment's length, which sizes the grid and the workspace; longer segments are cut to it) and the same n_seg;
+ * 1 <= cols <= ES_MMD_MAX_COLS, 1 <= degree <= ES_MMD_MAX_DEGREE, 1 <= rows, cap <= ES_DIST_MAX_ROWS,
+ * 1 <= n_seg <= ES_DIST_MAX_SEG.  With k(u, v) = (gamma <u, v> + coef0)^degree (<u, v> the fp64 sum over the columns
+ * in order of the widened fp32 entries, the power by degree - 1 multiplications), for segment s with the real
+ * members x_i, i < m, and the generated members y_j, j < n:
+ *   sums[s] (fp64 [n_seg][4]) = { S_xx = sum_{i != j} k(x_i, x_j), S_yy = sum_{i != j} k(y_i, y_j),
+ *                                 S_xy = sum_{i, j} k(x_i, y_j), 0 }
+ *   counts[s] (int32 [n_seg][2]) = { m, n }
+ * The diagonal of S_xx / S_yy is excluded by member position, not subtracted.  No kernel value is stored: one grid
+ * walks 128 x 128 tiles of all three matrices of all segments, a thread adds its 8 x 8 pairs tile after tile, the
+ * threads of a workgroup are added by a butterfly and the workgroups' partials in tile order by a second launch.
+ * The unbiased MMD^2 = S_xx / (m (m - 1)) + S_yy / (n (n - 1)) - 2 S_xy / (m n) is left to the host.
+ * work: es_mmd_poly_workspace(n_seg, r_cap, f_cap) bytes (0: outside the limits): the workgroups' partials. */
+#define ES_DIST_MAX_ROWS (1 << 20)
+#define ES_DIST_MAX_SEG 1024
+#define ES_MOMENTS_MAX_COLS 32
+#define ES_MOMENTS_CHUNKS 16
+#define ES_MMD_MAX_COLS 64
+#define ES_MMD_MAX_DEGREE 8
+size_t es_segment_moments_workspace(int n_seg, int cols);
+size_t es_mmd_poly_workspace(int n_seg, int r_cap, int f_cap);
+int es_segment_moments(const void* x, int x_f64, int64_t ld, int rows, int cols,
+                       const int32_t* idx /* [rows] or NULL */, const int32_t* seg /* [n_seg, 2] */, int n_seg,
+                       int32_t* count /* [n_seg] */, double* mean /* [n_seg, cols] */,
+                       double* cov /* [n_seg, cols, cols] */, void* work, size_t work_bytes, es_stream_t stream);
+int es_frechet(const double* mean_a, const double* cov_a, const double* mean_b, const double* cov_b, int n, int cols,
+               double* out /* [n, 4] */, es_stream_t stream);
+int es_mmd_poly(const float* real, int64_t r_ld, int r_rows, const int32_t* r_idx, const int32_t* r_seg, int r_cap,
+                const float* fake, int64_t f_ld, int f_rows, const int32_t* f_idx, const int32_t* f_seg, int f_cap,
+                int cols, int n_seg, int degree, double gamma, double coef0, double* sums /* [n_seg, 4] */,
+                int32_t* counts /* [n_seg, 2] */, void* work, size_t work_bytes, es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
  * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
  * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
