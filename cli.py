@@ -8,11 +8,13 @@ The reference's CUDA_LAUNCH_BLOCKING / cudnn flags / anomaly detection (cli.py:2
 Simulation (conditions in, calorimeter images out; MoEWrapper.simulate) from a saved checkpoint:
     python cli.py -o model.architecture=neutron dataset.input_image_shape=[44,44] model.n_experts=3 \
         --simulate --checkpoint DIR [--checkpoint-epoch E] (--cond FILE.npy | --num-samples N) --out FILE.npz \
-        [--features] [--real FILE.npy [--prdc-k K] [--distances]]
+        [--features] [--real FILE.npy [--prdc-k K] [--distances] [--sliced [--sliced-proj P]]]
 --real FILE.npy (real images [N,H,W] in the log1p domain, aligned with --cond) adds the sample-level precision /
 recall / density / coverage of the simulated images against them at K neighbours (default 5), jointly and per
 expert (expertsim/train/fidelity.py), as prdc_* entries of the .npz and on stdout.  --distances adds the Frechet
 and kernel distances of the ten shower observables (expertsim/train/distances.py) next to them as dist_* entries.
+--sliced adds the sliced Wasserstein distance of whole images in the log1p domain at P random directions (default
+256; expertsim/train/sliced.py) as swd* entries.
 
 Dataset preparation (raw responses + particle conditions in, the three pickles of dataset.source=pickle out;
 expertsim/utils/data_preparation.py) for the detector named by dataset.zdc_type:
@@ -65,6 +67,9 @@ def parse_args(args=None):
     g.add_argument("--prdc-k", type=int, default=5, help="neighbours of the --real metrics")
     g.add_argument("--distances", action="store_true",
                    help="with --real: also the Frechet and kernel distances of the ten shower observables (dist_*)")
+    g.add_argument("--sliced", action="store_true",
+                   help="with --real: also the sliced Wasserstein distance of whole images (swd, swd_err, swd_max)")
+    g.add_argument("--sliced-proj", type=int, default=256, help="random directions of --sliced")
     x = p.add_argument_group("expert diagnostics (instead of training)")
     x.add_argument("--diagnose", action="store_true",
                    help="per-expert histograms and KDEs for --conditions FILE from --checkpoint DIR, written to --out")
@@ -162,8 +167,17 @@ def simulate(args):
             for name, v in dist.distances(obs_real, obs_gen, res["expert"], moe.n_experts).items():
                 extra[f"dist_{name}"] = np.float64(v)
                 logger.info("dist_%s = %.6g", name, v)
+        if args.sliced:
+            from expertsim.train.sliced import sliced
+            for name, v in sliced(torch.from_numpy(real).to(device), torch.log1p(res["images"]), res["expert"],
+                                  moe.n_experts, n_proj=args.sliced_proj, seed=args.seed).items():
+                extra[name] = np.float64(v)
+                logger.info("%s = %.6g", name, v)
+            extra["swd_proj"] = np.int64(args.sliced_proj)
     elif args.distances:
         raise SystemExit("--distances needs --real FILE.npy")
+    elif args.sliced:
+        raise SystemExit("--sliced needs --real FILE.npy")
     np.savez(args.out, images=res["images"].cpu().numpy(), expert=res["expert"].cpu().numpy(),
              sums=res["sums"].cpu().numpy(), cond=cond, **extra)
     logger.info("Simulated %d images (epoch %d checkpoint) -> %s", cond.shape[0], epoch, args.out)

@@ -239,6 +239,8 @@ _SIGS = {
     "es_frechet": (C.c_int, [P, P, P, P, C.c_int, C.c_int, P, P]),
     "es_mmd_poly": (C.c_int, [P, I64, C.c_int, P, P, C.c_int, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_double, C.c_double, P, P, P, C.c_size_t, P]),
+    "es_sliced_project": (C.c_int, [P, C.c_int, P, P, I64, C.c_int, P, I64, P]),
+    "es_sliced_directions": (C.c_int, [P, I64, C.c_int, C.c_int, C.c_uint64, C.c_uint32, P]),
 }
 
 # es_group_diversity's split of a large group (ES_PREP_SPLIT_MIN / ES_PREP_CHUNKS of include/expertsim_hip.h)

@@ -634,7 +634,7 @@ class MoEWrapper(nn.Module):
     @torch.no_grad()
     def evaluate_device(self, epoch, y_test, x_test, cfg, *, seed=0, sample_offset=0, routing="sample",
                         fused=True, graph=True, details=False, features=False, prdc=False, prdc_k=5,
-                        distances=False):
+                        distances=False, sliced=False, sliced_proj=256):
         """The metrics of evaluate (same keys) from the simulate path, without a host round trip until
         the result: real sums by es_channel_sums, repetition j of the n_calc = min(epoch // 5 + 1, 5) by
         simulate(sums=True) -- j = 0 with simulate's own noise draw, j > 0 with es_randn_dev(seed + j) on
@@ -674,7 +674,16 @@ class MoEWrapper(nn.Module):
         the same expert vector: dist_fpd / dist_fpd_err / dist_fd_full / dist_kpd / dist_kpd_err / dist_mmd_full
         (joint) and dist_<name>_<e> (expert e; NaN where the expert has too few rows).  One further small copy;
         details=True adds dist_obs_real / dist_obs_gen [N, 10] (normalised), dist_scale [10], dist_fpd_table,
-        dist_fpd_frechet and dist_kpd_table.  The other keys keep their values bit for bit."""
+        dist_fpd_frechet and dist_kpd_table.  The other keys keep their values bit for bit.
+
+        sliced=True adds the sliced Wasserstein distance of train.sliced over whole images at sliced_proj directions
+        (train.sliced.directions(sliced_proj, H * W, seed)): the real side is x as uploaded (the stored log1p domain,
+        the space the discriminator sees), the generated side log1p of repetition 0's images (the tensor prdc=True
+        uses, when both are on), the segments those of the same expert vector: swd / swd_err / swd_max (joint) and
+        swd_<e> / swd_err_<e> / swd_max_<e> (expert e; NaN when either side has no row there).  One further small
+        copy; details=True adds swd_real / swd_gen (the two image tensors), swd_theta, swd_w [E + 1, P] and
+        swd_proj_real / swd_proj_gen.  The value depends on the pixel domain and on sliced_proj: compare equal
+        settings only.  The other keys keep their values bit for bit."""
         from ..train.utils import (FEATURE_NAMES, channel_sums, image_features, ws_across_experts_device,
                                    ws_feature_summary, ws_summary)
         dev = next(self.parameters()).device
@@ -709,7 +718,7 @@ class MoEWrapper(nn.Module):
                     feat_gen[j].copy_(sim["features"])
                 if expert is None:
                     expert = sim["expert"]
-                if prdc and j == 0:
+                if (prdc or sliced) and j == 0:
                     gen_log = torch.log1p(sim["images"])
                 if distances and j == 0:
                     gen_feat0 = feat_gen[0] if features else image_features(sim["images"])[0]
@@ -751,6 +760,15 @@ class MoEWrapper(nn.Module):
                 log[f"dist_{name}"] = v
             if details:
                 log.update(dist_obs_real=obs_real, dist_obs_gen=obs_gen, dist_scale=scale)
+        if sliced:
+            from ..train import sliced as swd
+            with torch.cuda.device(dev):
+                s = swd.sliced(x, gen_log, expert, E, n_proj=int(sliced_proj), seed=seed,
+                               details=bool(details))                                 # one small D2H copy
+            log.update({k: v for k, v in s.items() if isinstance(v, float)})
+            if details:
+                log.update(swd_real=x, swd_gen=gen_log, swd_theta=s["theta"], swd_w=s["w"],
+                           swd_proj_real=s["proj_real"], swd_proj_gen=s["proj_fake"])
         if details:
             log.update(sums_real=sums_real, sums_gen=sums_gen, expert=expert, ws=ws)
             if features:

@@ -119,7 +119,11 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     train.eval_distances (with eval_on_device only): also the joint-distribution distances of
     evaluate_device(distances=True) (train/distances.py: dist_fpd, dist_kpd and their companions, jointly and per
     expert), each key averaged over the batches in which it is finite; NaN if it is finite in none.  Both
-    statistics depend on the number of samples in a batch: compare runs at equal batch size."""
+    statistics depend on the number of samples in a batch: compare runs at equal batch size.
+    train.eval_sliced (with eval_on_device only): also the sliced Wasserstein distance of whole images of
+    evaluate_device(sliced=True, sliced_proj=train.eval_sliced_proj) (train/sliced.py: swd, swd_err, swd_max, jointly
+    and per expert), each key averaged over the batches in which it is finite; NaN if it is finite in none.  The
+    value depends on train.eval_sliced_proj: compare runs at equal settings."""
     on_device = bool(cfg.train.get("eval_on_device", False))
     features = bool(cfg.train.get("eval_features", False))
     diagnostics = bool(cfg.train.get("eval_diagnostics", False))
@@ -127,6 +131,11 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     prdc = bool(cfg.train.get("eval_prdc", False))
     prdc_k = int(cfg.train.get("eval_prdc_k", 5))
     distances = bool(cfg.train.get("eval_distances", False))
+    sliced = bool(cfg.train.get("eval_sliced", False))
+    sliced_proj = int(cfg.train.get("eval_sliced_proj", 256))
+    if sliced and not on_device:
+        raise ValueError("train.eval_sliced needs train.eval_on_device: the sliced Wasserstein distance exists on the "
+                         "device path only (MoEWrapper.evaluate_device)")
     if distances and not on_device:
         raise ValueError("train.eval_distances needs train.eval_on_device: the distribution distances exist on the "
                          "device path only (MoEWrapper.evaluate_device)")
@@ -158,6 +167,10 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
         from .distances import KEYS
         prdc_keys += [f"dist_{name}" for name in KEYS]
         prdc_keys += [f"dist_{name}_{i}" for i in range(moe.n_experts) for name in KEYS]
+    if sliced:
+        from .sliced import KEYS as SWD_KEYS
+        prdc_keys += list(SWD_KEYS)
+        prdc_keys += [f"{name}_{i}" for i in range(moe.n_experts) for name in SWD_KEYS]
     acc: Dict[str, List[float]] = {k: [] for k in keys + prdc_keys}
     seen = 0                                   # test samples in earlier batches
     conds = []                                 # the batches' device conditions (eval_diagnostics)
@@ -170,6 +183,8 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
             extra = dict(prdc=True, prdc_k=prdc_k) if prdc else {}
             if distances:
                 extra["distances"] = True
+            if sliced:
+                extra.update(sliced=True, sliced_proj=sliced_proj)
             m = moe.evaluate_device(epoch, cond_dev, real_images, cfg,
                                     seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=seen,
                                     features=features, **extra)

@@ -1185,6 +1185,33 @@ int es_mmd_poly(const float* real, int64_t r_ld, int r_rows, const int32_t* r_id
                 int32_t* counts /* [n_seg, 2] */, void* work, size_t work_bytes, es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sliced Wasserstein distance of whole images -- csrc/sliced.hip.  The 1-D distances of the projected columns
+ * are es_wasserstein_1d's (channels = n_proj, ld = out_ld), the moments over the directions es_segment_moments'.
+ * ---------------------------------------------------------------------------------------- */
+/* es_sliced_project.  x [n,1,h,w] (any strides, fp32 or bf16, widened exactly); pixel (i, j) is element
+ * d = i * w + j of D = h * w.  theta [n_proj][theta_ld] fp64, theta_ld >= D.  out[b * out_ld + p] (fp64,
+ * out_ld >= n_proj) = sum_d x[b][d] * theta[p][d]; the columns n_proj .. out_ld and the rows from n on are not
+ * written.  The sum runs on v_mfma_f64_16x16x4_f64: every output element is ONE accumulator chain from +0.0 over
+ * the k-steps d0 = 0, 4, 8, ... in ascending order (four products a step, added by the instruction), D padded to a
+ * multiple of 4 with +0.0 operands; no split over D, no atomics.  A result is bit-equal across reruns and does
+ * not depend on n, on n_proj, on the row's position in the batch, on the direction's position in theta or on the
+ * strides.  With n_proj <= 256 every image is read from memory once.
+ * 1 <= D <= ES_SLICED_MAX_D, 1 <= n_proj <= ES_SLICED_MAX_PROJ, n <= 2^20, c == 1; outside that, with a NULL
+ * pointer, theta_ld < D or out_ld < n_proj: ES_ERR_ARG before any launch.  n == 0: ES_OK without a launch.
+ *
+ * es_sliced_directions.  theta [n_proj][theta_ld] fp64 (theta_ld >= d; columns from d on are not written): row p is
+ * the draws p * D2 .. p * D2 + d - 1 of es_randn(., n_proj * D2, seed, stream_id), D2 = d rounded up to even,
+ * widened to fp64 and divided by the square root of their fp64 sum of squares.  That sum: thread t of 256 adds
+ * the squares of draws t, t + 256, ... in that order, the 64 lanes of a wave by a butterfly, the four waves in
+ * order; bit-equal across reruns.  1 <= d <= ES_SLICED_MAX_D, 1 <= n_proj <= ES_SLICED_MAX_PROJ. */
+#define ES_SLICED_MAX_D 4096
+#define ES_SLICED_MAX_PROJ 1024
+int es_sliced_project(const es_view_t* x, es_dtype_t dt, const void* xp, const double* theta, int64_t theta_ld,
+                      int n_proj, double* out, int64_t out_ld, es_stream_t stream);
+int es_sliced_directions(double* theta, int64_t theta_ld, int n_proj, int d, uint64_t seed, uint32_t stream_id,
+                         es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
  * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
  * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
