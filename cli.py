@@ -8,13 +8,16 @@ The reference's CUDA_LAUNCH_BLOCKING / cudnn flags / anomaly detection (cli.py:2
 Simulation (conditions in, calorimeter images out; MoEWrapper.simulate) from a saved checkpoint:
     python cli.py -o model.architecture=neutron dataset.input_image_shape=[44,44] model.n_experts=3 \
         --simulate --checkpoint DIR [--checkpoint-epoch E] (--cond FILE.npy | --num-samples N) --out FILE.npz \
-        [--features] [--real FILE.npy [--prdc-k K] [--distances] [--sliced [--sliced-proj P]]]
+        [--features] [--real FILE.npy [--prdc-k K] [--distances] [--sliced [--sliced-proj P]]
+                                      [--classifier [--classifier-degree D]]]
 --real FILE.npy (real images [N,H,W] in the log1p domain, aligned with --cond) adds the sample-level precision /
 recall / density / coverage of the simulated images against them at K neighbours (default 5), jointly and per
 expert (expertsim/train/fidelity.py), as prdc_* entries of the .npz and on stdout.  --distances adds the Frechet
 and kernel distances of the ten shower observables (expertsim/train/distances.py) next to them as dist_* entries.
 --sliced adds the sliced Wasserstein distance of whole images in the log1p domain at P random directions (default
-256; expertsim/train/sliced.py) as swd* entries.
+256; expertsim/train/sliced.py) as swd* entries.  --classifier adds the classifier two-sample test of the ten shower
+observables (held-out AUC, KS, accuracy and log-loss of a logistic regression on the observables and, at D = 2,
+their pairwise products; expertsim/train/classifier.py) as c2st_* entries.
 
 Dataset preparation (raw responses + particle conditions in, the three pickles of dataset.source=pickle out;
 expertsim/utils/data_preparation.py) for the detector named by dataset.zdc_type:
@@ -70,6 +73,10 @@ def parse_args(args=None):
     g.add_argument("--sliced", action="store_true",
                    help="with --real: also the sliced Wasserstein distance of whole images (swd, swd_err, swd_max)")
     g.add_argument("--sliced-proj", type=int, default=256, help="random directions of --sliced")
+    g.add_argument("--classifier", action="store_true",
+                   help="with --real: also the classifier two-sample test of the ten shower observables (c2st_*)")
+    g.add_argument("--classifier-degree", type=int, default=2, choices=(1, 2),
+                   help="features of --classifier: 1 the observables, 2 also their pairwise products")
     x = p.add_argument_group("expert diagnostics (instead of training)")
     x.add_argument("--diagnose", action="store_true",
                    help="per-expert histograms and KDEs for --conditions FILE from --checkpoint DIR, written to --out")
@@ -174,6 +181,19 @@ def simulate(args):
                 extra[name] = np.float64(v)
                 logger.info("%s = %.6g", name, v)
             extra["swd_proj"] = np.int64(args.sliced_proj)
+        if args.classifier:
+            from expertsim.train import distances as dist
+            from expertsim.train.classifier import c2st
+            feat = res["features"] if args.features else None
+            obs_real = dist.observables(torch.from_numpy(real).to(device), log_domain=True)
+            obs_gen = dist.observables(res["images"], log_domain=False, sums=res["sums"], features=feat)
+            for name, v in c2st(obs_real, obs_gen, res["expert"], moe.n_experts,
+                                degree=args.classifier_degree).items():
+                extra[name] = np.float64(v)
+                logger.info("%s = %.6g", name, v)
+            extra["c2st_degree"] = np.int64(args.classifier_degree)
+    elif args.classifier:
+        raise SystemExit("--classifier needs --real FILE.npy")
     elif args.distances:
         raise SystemExit("--distances needs --real FILE.npy")
     elif args.sliced:

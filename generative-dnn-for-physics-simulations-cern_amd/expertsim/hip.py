@@ -241,6 +241,16 @@ _SIGS = {
                               C.c_int, C.c_double, C.c_double, P, P, P, C.c_size_t, P]),
     "es_sliced_project": (C.c_int, [P, C.c_int, P, P, I64, C.c_int, P, I64, P]),
     "es_sliced_directions": (C.c_int, [P, I64, C.c_int, C.c_int, C.c_uint64, C.c_uint32, P]),
+    "es_rank_stats_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "es_rank_stats": (C.c_int, [P, I64, C.c_int, P, P, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                P, P, C.c_size_t, P]),
+    "es_logit_block_rows": (C.c_int, []),
+    "es_logit_fit_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "es_logit_scores_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "es_logit_fit": (C.c_int, [P, I64, C.c_int, P, P, C.c_int, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int,
+                               C.c_int, C.c_double, C.c_double, C.c_int, P, P, P, C.c_size_t, P]),
+    "es_logit_scores": (C.c_int, [P, I64, C.c_int, P, P, C.c_int, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int,
+                                  C.c_int, P, P, P, P, P, P, P, C.c_size_t, P]),
 }
 
 # es_group_diversity's split of a large group (ES_PREP_SPLIT_MIN / ES_PREP_CHUNKS of include/expertsim_hip.h)
@@ -304,6 +314,32 @@ def segment_moments_workspace(n_seg: int, cols: int) -> int:
 def mmd_poly_workspace(n_seg: int, r_cap: int, f_cap: int) -> int:
     """Bytes of es_mmd_poly's workspace (0: outside the limits)."""
     return int(lib().es_mmd_poly_workspace(int(n_seg), int(r_cap), int(f_cap)))
+
+
+# classifier two-sample test (ES_LOGIT_* of include/expertsim_hip.h)
+LOGIT_MAX_COLS = 80
+LOGIT_MAX_ITER = 100
+LOGIT_BLOCK_ROWS = 256
+
+
+def rank_stats_workspace(n_seg: int, channels: int, u_cap: int, v_cap: int) -> int:
+    """Bytes of es_rank_stats's workspace (0: the LDS path, or outside the limits)."""
+    return int(lib().es_rank_stats_workspace(int(n_seg), int(channels), int(u_cap), int(v_cap)))
+
+
+def logit_fit_workspace(n_seg: int, cols: int, r_cap: int, f_cap: int) -> int:
+    """Bytes of es_logit_fit's workspace (0: outside the limits)."""
+    return int(lib().es_logit_fit_workspace(int(n_seg), int(cols), int(r_cap), int(f_cap)))
+
+
+def logit_scores_workspace(n_seg: int, r_cap: int, f_cap: int) -> int:
+    """Bytes of es_logit_scores's workspace (0: outside the limits)."""
+    return int(lib().es_logit_scores_workspace(int(n_seg), int(r_cap), int(f_cap)))
+
+
+def logit_block_rows() -> int:
+    """The members one workgroup of es_logit_fit takes (ES_LOGIT_BLOCK_ROWS of the built library)."""
+    return int(lib().es_logit_block_rows())
 
 
 def kmeans_workspace(rows: int, cols: int, k: int) -> int:

@@ -634,7 +634,7 @@ class MoEWrapper(nn.Module):
     @torch.no_grad()
     def evaluate_device(self, epoch, y_test, x_test, cfg, *, seed=0, sample_offset=0, routing="sample",
                         fused=True, graph=True, details=False, features=False, prdc=False, prdc_k=5,
-                        distances=False, sliced=False, sliced_proj=256):
+                        distances=False, sliced=False, sliced_proj=256, classifier=False, classifier_degree=2):
         """The metrics of evaluate (same keys) from the simulate path, without a host round trip until
         the result: real sums by es_channel_sums, repetition j of the n_calc = min(epoch // 5 + 1, 5) by
         simulate(sums=True) -- j = 0 with simulate's own noise draw, j > 0 with es_randn_dev(seed + j) on
@@ -683,7 +683,16 @@ class MoEWrapper(nn.Module):
         swd_<e> / swd_err_<e> / swd_max_<e> (expert e; NaN when either side has no row there).  One further small
         copy; details=True adds swd_real / swd_gen (the two image tensors), swd_theta, swd_w [E + 1, P] and
         swd_proj_real / swd_proj_gen.  The value depends on the pixel domain and on sliced_proj: compare equal
-        settings only.  The other keys keep their values bit for bit."""
+        settings only.  The other keys keep their values bit for bit.
+
+        classifier=True adds the classifier two-sample test of train.classifier.c2st over the same ten observables
+        (the tables distances=True uses, BEFORE normalise -- c2st standardises them itself -- and computed once when
+        both are on): repetition 0 against the real rows over the segments of the same expert vector, a logistic
+        regression on the observables and, at classifier_degree=2, their pairwise products, trained on the first
+        half of every segment and scored on the second: c2st_auc / c2st_ks / c2st_acc / c2st_logloss / c2st_iter /
+        c2st_converged (joint) and c2st_<name>_<e> (expert e; NaN where a half is empty on either side).  One
+        further small copy; details=True adds c2st_obs_real / c2st_obs_gen [N, 10], c2st_theta and c2st_table.  The
+        values depend on N and on the order of the rows (see c2st).  The other keys keep their values bit for bit."""
         from ..train.utils import (FEATURE_NAMES, channel_sums, image_features, ws_across_experts_device,
                                    ws_feature_summary, ws_summary)
         dev = next(self.parameters()).device
@@ -720,7 +729,7 @@ class MoEWrapper(nn.Module):
                     expert = sim["expert"]
                 if (prdc or sliced) and j == 0:
                     gen_log = torch.log1p(sim["images"])
-                if distances and j == 0:
+                if (distances or classifier) and j == 0:
                     gen_feat0 = feat_gen[0] if features else image_features(sim["images"])[0]
             ws = ws_across_experts_device(sums_real, sums_gen, expert, E)
             if features:
@@ -749,17 +758,27 @@ class MoEWrapper(nn.Module):
             if details:
                 log.update(prdc_totals=raw["totals"], prdc_r_radius2=raw["r_radius2"],
                            prdc_f_radius2=raw["f_radius2"])
-        if distances:
+        if distances or classifier:
             from ..train import distances as dist
             with torch.cuda.device(dev):
-                obs_real = dist.observables(x, sums=sums_real, features=feat_real if features else None)
-                obs_gen = dist.observables(None, sums=sums_gen[0], features=gen_feat0)
-                obs_real, obs_gen, scale = dist.normalise(obs_real, obs_gen)
+                raw_real = dist.observables(x, sums=sums_real, features=feat_real if features else None)
+                raw_gen = dist.observables(None, sums=sums_gen[0], features=gen_feat0)
+        if distances:
+            with torch.cuda.device(dev):
+                obs_real, obs_gen, scale = dist.normalise(raw_real, raw_gen)
                 d = dist.distances(obs_real, obs_gen, expert, E, details=bool(details))   # one small D2H copy
             for name, v in d.items():
                 log[f"dist_{name}"] = v
             if details:
                 log.update(dist_obs_real=obs_real, dist_obs_gen=obs_gen, dist_scale=scale)
+        if classifier:
+            from ..train import classifier as clf
+            with torch.cuda.device(dev):
+                c = clf.c2st(raw_real, raw_gen, expert, E, degree=int(classifier_degree),
+                             details=bool(details))                                   # one small D2H copy
+            log.update({k: v for k, v in c.items() if isinstance(v, float)})
+            if details:
+                log.update(c2st_obs_real=raw_real, c2st_obs_gen=raw_gen, c2st_theta=c["theta"], c2st_table=c["table"])
         if sliced:
             from ..train import sliced as swd
             with torch.cuda.device(dev):

@@ -123,7 +123,12 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     train.eval_sliced (with eval_on_device only): also the sliced Wasserstein distance of whole images of
     evaluate_device(sliced=True, sliced_proj=train.eval_sliced_proj) (train/sliced.py: swd, swd_err, swd_max, jointly
     and per expert), each key averaged over the batches in which it is finite; NaN if it is finite in none.  The
-    value depends on train.eval_sliced_proj: compare runs at equal settings."""
+    value depends on train.eval_sliced_proj: compare runs at equal settings.
+    train.eval_classifier (with eval_on_device only): also the classifier two-sample test of
+    evaluate_device(classifier=True, classifier_degree=train.eval_classifier_degree) (train/classifier.py: c2st_auc,
+    c2st_ks, c2st_acc, c2st_logloss, c2st_iter, c2st_converged, jointly and per expert), each key averaged over the
+    batches in which it is finite; NaN if it is finite in none.  The classifier trains on the first half of a batch's
+    rows and is scored on the second, so the values depend on the batch size: compare runs at equal batch size."""
     on_device = bool(cfg.train.get("eval_on_device", False))
     features = bool(cfg.train.get("eval_features", False))
     diagnostics = bool(cfg.train.get("eval_diagnostics", False))
@@ -133,6 +138,11 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     distances = bool(cfg.train.get("eval_distances", False))
     sliced = bool(cfg.train.get("eval_sliced", False))
     sliced_proj = int(cfg.train.get("eval_sliced_proj", 256))
+    classifier = bool(cfg.train.get("eval_classifier", False))
+    classifier_degree = int(cfg.train.get("eval_classifier_degree", 2))
+    if classifier and not on_device:
+        raise ValueError("train.eval_classifier needs train.eval_on_device: the classifier two-sample test exists on "
+                         "the device path only (MoEWrapper.evaluate_device)")
     if sliced and not on_device:
         raise ValueError("train.eval_sliced needs train.eval_on_device: the sliced Wasserstein distance exists on the "
                          "device path only (MoEWrapper.evaluate_device)")
@@ -171,6 +181,10 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
         from .sliced import KEYS as SWD_KEYS
         prdc_keys += list(SWD_KEYS)
         prdc_keys += [f"{name}_{i}" for i in range(moe.n_experts) for name in SWD_KEYS]
+    if classifier:
+        from .classifier import KEYS as C2ST_KEYS
+        prdc_keys += list(C2ST_KEYS)
+        prdc_keys += [f"{name}_{i}" for i in range(moe.n_experts) for name in C2ST_KEYS]
     acc: Dict[str, List[float]] = {k: [] for k in keys + prdc_keys}
     seen = 0                                   # test samples in earlier batches
     conds = []                                 # the batches' device conditions (eval_diagnostics)
@@ -185,6 +199,8 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
                 extra["distances"] = True
             if sliced:
                 extra.update(sliced=True, sliced_proj=sliced_proj)
+            if classifier:
+                extra.update(classifier=True, classifier_degree=classifier_degree)
             m = moe.evaluate_device(epoch, cond_dev, real_images, cfg,
                                     seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=seen,
                                     features=features, **extra)

@@ -1212,6 +1212,87 @@ int es_sliced_directions(double* theta, int64_t theta_ld, int n_proj, int d, uin
                          es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Classifier two-sample test: exact rank statistics (csrc/rank.hip) and ridge-penalised logistic regression per
+ * segment (csrc/classifier.hip).
+ * ---------------------------------------------------------------------------------------- */
+/* es_rank_stats.  The arguments, the segment rule, the clamping, the caps, the limits and the workspace rule are
+ * es_wasserstein_1d's: u / v fp64 [rows][ld] (ld >= channels), DEVICE idx / seg, host u_cap / v_cap, one launch
+ * with each problem sorted in LDS while u_cap + v_cap <= ES_WS_LDS_MAX, global-memory passes over `work`
+ * (es_rank_stats_workspace bytes) up to 2^20, ES_ERR_ARG above that or with too small a workspace and nothing is
+ * launched.  Values must be finite.  For column c of segment s with the nu values u_i and the nv values v_j:
+ *   out[(s * channels + c) * 4 ..] (int64) = { nu, nv, U2, KS }
+ *   U2 = sum over the pairs (i, j) of 2 [u_i > v_j] + [u_i == v_j]: U2 / (2 nu nv) is the ROC AUC of u against v
+ *        (the Mann-Whitney U statistic of u is U2 / 2), ties counted half;
+ *   KS = max over the distinct values a of |cu(a) nv - cv(a) nu|, cu(a) / cv(a) the counts of values <= a:
+ *        KS / (nu nv) is the two-sample Kolmogorov-Smirnov statistic.
+ * A segment empty on either side gives { nu, nv, 0, 0 }.  -0.0 and +0.0 are the same value.  Integer arithmetic
+ * throughout (nu nv <= 2^38); counts are looked at only where a run of equal values starts or ends, so the order
+ * the sort leaves inside a run cannot matter; no atomics; a rerun is bit-equal. */
+size_t es_rank_stats_workspace(int n_seg, int channels, int u_cap, int v_cap);
+int es_rank_stats(const double* u, int64_t u_ld, int u_rows, const int32_t* u_idx, const int32_t* u_seg,
+                  const double* v, int64_t v_ld, int v_rows, const int32_t* v_idx, const int32_t* v_seg,
+                  int n_seg, int channels, int u_cap, int v_cap, int64_t* out /* [n_seg * channels, 4] */,
+                  void* work, size_t work_bytes, es_stream_t stream);
+/* es_logit_fit / es_logit_scores.  real / fake [rows][ld] with their own ld / rows / idx / seg / cap as for
+ * es_mmd_poly (same segment rule, same n_seg, cap the host upper bound of a segment's length), fp32 or fp64 for
+ * both (x_f64 != 0), 1 <= cols <= ES_LOGIT_MAX_COLS, cols <= ld, 1 <= rows, cap <= ES_DIST_MAX_ROWS,
+ * 1 <= n_seg <= ES_DIST_MAX_SEG.  Outside the limits, with a NULL required pointer or too small a workspace:
+ * ES_ERR_ARG before any launch.  Values must be finite.
+ *
+ * Per segment s the m real members carry y = 1 and the k generated members y = 0; with n = m + k, z~ = (1, z) and
+ * theta = (b, w) the objective is
+ *   F(theta) = (1/n) sum_i [softplus(t_i) - y_i t_i] + (l2 / (2 n)) |w|^2,   t_i = b + <w, z_i>
+ * (the intercept unpenalised, l2 = scikit-learn's 1 / C, softplus without overflow).
+ *
+ * es_logit_fit minimises F from theta = 0 by Newton steps in fp64: g = (1/n) Z~^T (p - y) + (l2/n) (0, w),
+ * H = (1/n) Z~^T diag(p (1 - p)) Z~ + (l2/n) diag(0, 1..1), the step d = -H^-1 g by a Cholesky factorisation in the
+ * kernel.  A step is safeguarded on F: theta + d is taken when F(theta + d) <= F(theta) (1 + (n + 64) 2^-52), i.e.
+ * F did not increase beyond its own rounding; otherwise the point of least F < F(theta) among theta + 2^-j d,
+ * j = 1 .. 7 (all evaluated in the same pass), and g, H are re-evaluated there.  The fit stops with status 1 once
+ * |g|_inf <= gtol, with status 0 after max_iter (1 .. ES_LOGIT_MAX_ITER) moves, when no trial point lowers F or
+ * when the factorisation meets a pivot <= 0 (possible only with l2 = 0); theta is always the last accepted point
+ * and |g|_inf, F belong to it.  A segment empty on either side is degenerate: status -1, theta NaN.
+ *   theta (fp64 [n_seg][cols + 1]) intercept first
+ *   stat  (fp64 [n_seg][4]) = { F, |g|_inf, iterations (moves taken), status }
+ * The host issues 1 + 2 (max_iter + 1) launches and never synchronises; a per-segment device flag turns the
+ * launches after the stop into early-outs.  Members are numbered real first; blocks of ES_LOGIT_BLOCK_ROWS
+ * (es_logit_block_rows()) consecutive members go to one workgroup each, whose partial g, H, F go to the workspace;
+ * one workgroup per segment adds them in block order, solves and updates in the next launch.  No float atomics,
+ * every sum in a fixed order: a rerun is bit-equal.
+ * work: es_logit_fit_workspace(n_seg, cols, r_cap, f_cap) bytes (0: outside the limits).
+ *
+ * es_logit_scores.  The same tables and segments plus theta as es_logit_fit writes it.  The score of a member is
+ * t = b + sum_c w_c z_c, one fused multiply-add per column in ascending order from t = b.  Layout: the score of
+ * real member i of segment s is r_scores[s * r_cap + i], of generated member j f_scores[s * f_cap + j] (fp64
+ * [n_seg][cap]; entries past a segment's length are not written), and r_oseg / f_oseg (int32 [n_seg][2]) receive
+ * the bounds (s * cap, s * cap + length), so that
+ *   es_rank_stats(r_scores, 1, n_seg * r_cap, NULL, r_oseg, f_scores, 1, n_seg * f_cap, NULL, f_oseg, n_seg, 1,
+ *                 r_cap, f_cap, ..)
+ * reads every segment's scores back without a host-side length (n_seg * cap <= 2^31 - 1).
+ *   sums (fp64 [n_seg][4]) = { real members with t > 0, generated members with t <= 0,
+ *                              sum of softplus(-t) over the real members, sum of softplus(t) over the generated }
+ * Order of a sum: blocks of 256 consecutive members, inside a block a butterfly over the 64 lanes and the four
+ * waves in order, the blocks in order.  A NaN theta gives NaN scores and sums { 0, 0, NaN, NaN }.
+ * work: es_logit_scores_workspace(n_seg, r_cap, f_cap) bytes (0: outside the limits). */
+#define ES_LOGIT_MAX_COLS 80
+#define ES_LOGIT_MAX_ITER 100
+#define ES_LOGIT_BLOCK_ROWS 256
+int es_logit_block_rows(void);
+size_t es_logit_fit_workspace(int n_seg, int cols, int r_cap, int f_cap);
+size_t es_logit_scores_workspace(int n_seg, int r_cap, int f_cap);
+int es_logit_fit(const void* real, int64_t r_ld, int r_rows, const int32_t* r_idx, const int32_t* r_seg, int r_cap,
+                 const void* fake, int64_t f_ld, int f_rows, const int32_t* f_idx, const int32_t* f_seg, int f_cap,
+                 int x_f64, int cols, int n_seg, double l2, double gtol, int max_iter,
+                 double* theta /* [n_seg, cols + 1] */, double* stat /* [n_seg, 4] */, void* work, size_t work_bytes,
+                 es_stream_t stream);
+int es_logit_scores(const void* real, int64_t r_ld, int r_rows, const int32_t* r_idx, const int32_t* r_seg, int r_cap,
+                    const void* fake, int64_t f_ld, int f_rows, const int32_t* f_idx, const int32_t* f_seg, int f_cap,
+                    int x_f64, int cols, int n_seg, const double* theta /* [n_seg, cols + 1] */,
+                    double* r_scores /* [n_seg, r_cap] */, double* f_scores /* [n_seg, f_cap] */,
+                    int32_t* r_oseg /* [n_seg, 2] */, int32_t* f_oseg /* [n_seg, 2] */, double* sums /* [n_seg, 4] */,
+                    void* work, size_t work_bytes, es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
  * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
  * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
