@@ -9,7 +9,8 @@ Simulation (conditions in, calorimeter images out; MoEWrapper.simulate) from a s
     python cli.py -o model.architecture=neutron dataset.input_image_shape=[44,44] model.n_experts=3 \
         --simulate --checkpoint DIR [--checkpoint-epoch E] (--cond FILE.npy | --num-samples N) --out FILE.npz \
         [--features] [--real FILE.npy [--prdc-k K] [--distances] [--sliced [--sliced-proj P]]
-                                      [--classifier [--classifier-degree D]]]
+                                      [--classifier [--classifier-degree D]]
+                                      [--conditional [--conditional-bins B] [--conditional-column J]]]
 --real FILE.npy (real images [N,H,W] in the log1p domain, aligned with --cond) adds the sample-level precision /
 recall / density / coverage of the simulated images against them at K neighbours (default 5), jointly and per
 expert (expertsim/train/fidelity.py), as prdc_* entries of the .npz and on stdout.  --distances adds the Frechet
@@ -17,7 +18,10 @@ and kernel distances of the ten shower observables (expertsim/train/distances.py
 --sliced adds the sliced Wasserstein distance of whole images in the log1p domain at P random directions (default
 256; expertsim/train/sliced.py) as swd* entries.  --classifier adds the classifier two-sample test of the ten shower
 observables (held-out AUC, KS, accuracy and log-loss of a logistic regression on the observables and, at D = 2,
-their pairwise products; expertsim/train/classifier.py) as c2st_* entries.
+their pairwise products; expertsim/train/classifier.py) as c2st_* entries.  --conditional adds the conditional
+profile of the ten shower observables in B equally populated bins (default 8) of column J (default 0, the energy) of
+the conditions: the count-weighted per-bin Wasserstein distance, median bias, width difference and KS statistic as
+cond_* scalars and the response / resolution curves as cond_* arrays (expertsim/train/conditional.py).
 
 Dataset preparation (raw responses + particle conditions in, the three pickles of dataset.source=pickle out;
 expertsim/utils/data_preparation.py) for the detector named by dataset.zdc_type:
@@ -77,6 +81,12 @@ def parse_args(args=None):
                    help="with --real: also the classifier two-sample test of the ten shower observables (c2st_*)")
     g.add_argument("--classifier-degree", type=int, default=2, choices=(1, 2),
                    help="features of --classifier: 1 the observables, 2 also their pairwise products")
+    g.add_argument("--conditional", action="store_true",
+                   help="with --real: also the conditional profile of the ten shower observables by condition bin "
+                        "(cond_*)")
+    g.add_argument("--conditional-bins", type=int, default=8, help="equally populated bins of --conditional")
+    g.add_argument("--conditional-column", type=int, default=0,
+                   help="column of the conditions that --conditional bins (0: the energy)")
     x = p.add_argument_group("expert diagnostics (instead of training)")
     x.add_argument("--diagnose", action="store_true",
                    help="per-expert histograms and KDEs for --conditions FILE from --checkpoint DIR, written to --out")
@@ -139,6 +149,8 @@ def simulate(args):
     import torch
     if not args.checkpoint or not args.out or (args.cond is None) == (args.num_samples is None):
         raise SystemExit("--simulate needs --checkpoint DIR, --out FILE.npz and one of --cond FILE.npy / --num-samples N")
+    if args.conditional and args.real is None:
+        raise SystemExit("--conditional needs --real FILE.npy")
     if not torch.cuda.is_available():
         raise RuntimeError("expertsim simulates on a HIP device only (no CPU fallback)")
     cfg, moe, epoch = _load_checkpointed_moe(args, "--simulate")
@@ -192,6 +204,25 @@ def simulate(args):
                 extra[name] = np.float64(v)
                 logger.info("%s = %.6g", name, v)
             extra["c2st_degree"] = np.int64(args.classifier_degree)
+        if args.conditional:
+            from expertsim.train import distances as dist
+            from expertsim.train.conditional import profile
+            if not 0 <= args.conditional_column < cond.shape[1]:
+                raise SystemExit(f"--conditional-column {args.conditional_column} outside the {cond.shape[1]} columns")
+            feat = res["features"] if args.features else None
+            obs_real = dist.observables(torch.from_numpy(real).to(device), log_domain=True)
+            obs_gen = dist.observables(res["images"], log_domain=False, sums=res["sums"], features=feat)
+            by = torch.from_numpy(np.ascontiguousarray(cond[:, args.conditional_column])).to(device)
+            for name, v in profile(obs_real, obs_gen, by, args.conditional_bins, res["expert"], moe.n_experts,
+                                   names=dist.OBSERVABLE_NAMES, details=True).items():
+                if isinstance(v, float):
+                    extra[name] = np.float64(v)
+                    logger.info("%s = %.6g", name, v)
+                elif name in ("ws", "ks"):
+                    extra[f"cond_{name}_bins"] = v.cpu().numpy()
+                elif name not in ("seg", "idx", "q_all"):
+                    extra[f"cond_{name}"] = v.cpu().numpy()
+            extra["cond_column"] = np.int64(args.conditional_column)
     elif args.classifier:
         raise SystemExit("--classifier needs --real FILE.npy")
     elif args.distances:

@@ -11,6 +11,8 @@
 // The network is not stable: equal keys end in an order that depends on the network alone, so a caller's result
 // must not depend on the order inside a run of equal keys.  CANON: -0.0 is fetched as +0.0, so that equal values
 // have equal keys (es_rank_stats; es_wasserstein_1d keeps the bits it always sorted).
+// ONE_SIDED (defaulted false; es_segment_quantiles sets it): a problem is skipped only when BOTH sides are empty, not
+// when either is, so that one side can be sorted alone.
 // Every kernel is a template in an anonymous namespace: each including file gets its own instantiations.
 #pragma once
 #include "common.h"
@@ -33,6 +35,11 @@ __device__ __forceinline__ int ts_pow2(int m) {       // next power of two, >= 2
   int p = 2;
   while (p < m) p <<= 1;
   return p;
+}
+
+// a problem the sort leaves alone
+template <bool ONE_SIDED> __device__ __forceinline__ bool ts_skip(SegSpan su, SegSpan sv) {
+  return ONE_SIDED ? su.n + sv.n == 0 : (su.n == 0 || sv.n == 0);
 }
 
 template <bool CANON> __device__ __forceinline__ uint64_t ts_key(double x) {
@@ -79,14 +86,14 @@ __device__ __forceinline__ void ts_lds_stages(uint64_t* sk, uint8_t* st, int n, 
 // --------------------------------------------------------------------------------------- global path
 // mode 0: fetch the tile's elements and sort it (merge sizes 2 .. min(pm, TS_TILE));
 // mode 1: the strides below TS_TILE of merge size k.
-template <bool CANON>
+template <bool CANON, bool ONE_SIDED = false>
 __global__ void __launch_bounds__(TS_THREADS) ts_tile_kernel(TsArgs a, int P, int mode, int k, uint64_t* wk,
                                                              uint8_t* wt) {
   __shared__ uint64_t sk[TS_TILE];
   __shared__ uint8_t st[TS_TILE];
   const int prob = blockIdx.y, s = prob / a.channels, c = prob - s * a.channels;
   const SegSpan su = seg_span(a.u_seg, s, a.u_rows, a.u_cap), sv = seg_span(a.v_seg, s, a.v_rows, a.v_cap);
-  if (su.n == 0 || sv.n == 0) return;
+  if (ts_skip<ONE_SIDED>(su, sv)) return;
   const int pm = ts_pow2(su.n + sv.n);               // <= P
   const int base = blockIdx.x * TS_TILE;
   if (base >= pm || (mode == 1 && k > pm)) return;   // block-uniform
@@ -105,11 +112,12 @@ __global__ void __launch_bounds__(TS_THREADS) ts_tile_kernel(TsArgs a, int P, in
 }
 
 // one compare-exchange pass of merge size k at stride j >= TS_TILE
+template <bool ONE_SIDED = false>
 __global__ void __launch_bounds__(TS_THREADS) ts_global_stage_kernel(TsArgs a, int P, int k, int j, uint64_t* wk,
                                                                      uint8_t* wt) {
   const int prob = blockIdx.y, s = prob / a.channels;
   const SegSpan su = seg_span(a.u_seg, s, a.u_rows, a.u_cap), sv = seg_span(a.v_seg, s, a.v_rows, a.v_cap);
-  if (su.n == 0 || sv.n == 0) return;
+  if (ts_skip<ONE_SIDED>(su, sv)) return;
   const int pm = ts_pow2(su.n + sv.n);
   const int t = blockIdx.x * TS_THREADS + threadIdx.x;
   if (k > pm || t >= (pm >> 1)) return;
@@ -140,14 +148,14 @@ inline size_t ts_workspace(int n_seg, int channels, int u_cap, int v_cap) {
 }
 
 // The global path's launches: after them wk / wt [nprob][P] hold every live problem's sorted keys and tags.
-template <bool CANON>
+template <bool CANON, bool ONE_SIDED = false>
 inline void ts_sort_global(const TsArgs& a, int64_t nprob, int P, uint64_t* wk, uint8_t* wt, hipStream_t st) {
   const dim3 tiles(P / TS_TILE, (unsigned)nprob), pairs(P / 2 / TS_THREADS, (unsigned)nprob);
-  hipLaunchKernelGGL(ts_tile_kernel<CANON>, tiles, dim3(TS_THREADS), 0, st, a, P, 0, 0, wk, wt);
+  hipLaunchKernelGGL((ts_tile_kernel<CANON, ONE_SIDED>), tiles, dim3(TS_THREADS), 0, st, a, P, 0, 0, wk, wt);
   for (int k = 2 * TS_TILE; k <= P; k <<= 1) {
     for (int j = k >> 1; j >= TS_TILE; j >>= 1)
-      hipLaunchKernelGGL(ts_global_stage_kernel, pairs, dim3(TS_THREADS), 0, st, a, P, k, j, wk, wt);
-    hipLaunchKernelGGL(ts_tile_kernel<CANON>, tiles, dim3(TS_THREADS), 0, st, a, P, 1, k, wk, wt);
+      hipLaunchKernelGGL(ts_global_stage_kernel<ONE_SIDED>, pairs, dim3(TS_THREADS), 0, st, a, P, k, j, wk, wt);
+    hipLaunchKernelGGL((ts_tile_kernel<CANON, ONE_SIDED>), tiles, dim3(TS_THREADS), 0, st, a, P, 1, k, wk, wt);
   }
 }
 

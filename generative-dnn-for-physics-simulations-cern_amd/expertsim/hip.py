@@ -251,6 +251,11 @@ _SIGS = {
                                C.c_int, C.c_double, C.c_double, C.c_int, P, P, P, C.c_size_t, P]),
     "es_logit_scores": (C.c_int, [P, I64, C.c_int, P, P, C.c_int, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int,
                                   C.c_int, P, P, P, P, P, P, P, C.c_size_t, P]),
+    "es_segment_quantiles_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "es_segment_quantiles": (C.c_int, [P, I64, C.c_int, P, P, P, I64, C.c_int, P, P, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, P, C.c_int, P, P, P, C.c_size_t, P]),
+    "es_bin_dispatch_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "es_bin_dispatch": (C.c_int, [P, C.c_int, I64, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P, C.c_size_t, P]),
 }
 
 # es_group_diversity's split of a large group (ES_PREP_SPLIT_MIN / ES_PREP_CHUNKS of include/expertsim_hip.h)
@@ -325,6 +330,23 @@ LOGIT_BLOCK_ROWS = 256
 def rank_stats_workspace(n_seg: int, channels: int, u_cap: int, v_cap: int) -> int:
     """Bytes of es_rank_stats's workspace (0: the LDS path, or outside the limits)."""
     return int(lib().es_rank_stats_workspace(int(n_seg), int(channels), int(u_cap), int(v_cap)))
+
+
+# es_segment_quantiles / es_bin_dispatch (ES_QUANTILE_MAX_Q, ES_BINS_MAX of include/expertsim_hip.h)
+QUANTILE_MAX_Q = 16
+BINS_MAX = 64
+BINS_MAX_CLASSES = 1024
+BINS_MAX_ROWS = 1 << 20
+
+
+def segment_quantiles_workspace(n_seg: int, channels: int, u_cap: int, v_cap: int) -> int:
+    """Bytes of es_segment_quantiles's workspace (0: the LDS path, or outside the limits)."""
+    return int(lib().es_segment_quantiles_workspace(int(n_seg), int(channels), int(u_cap), int(v_cap)))
+
+
+def bin_dispatch_workspace(rows: int, n_classes: int) -> int:
+    """Bytes of es_bin_dispatch's workspace (0: outside the limits)."""
+    return int(lib().es_bin_dispatch_workspace(int(rows), int(n_classes)))
 
 
 def logit_fit_workspace(n_seg: int, cols: int, r_cap: int, f_cap: int) -> int:

@@ -634,7 +634,8 @@ class MoEWrapper(nn.Module):
     @torch.no_grad()
     def evaluate_device(self, epoch, y_test, x_test, cfg, *, seed=0, sample_offset=0, routing="sample",
                         fused=True, graph=True, details=False, features=False, prdc=False, prdc_k=5,
-                        distances=False, sliced=False, sliced_proj=256, classifier=False, classifier_degree=2):
+                        distances=False, sliced=False, sliced_proj=256, classifier=False, classifier_degree=2,
+                        conditional=False, conditional_bins=8, conditional_column=0):
         """The metrics of evaluate (same keys) from the simulate path, without a host round trip until
         the result: real sums by es_channel_sums, repetition j of the n_calc = min(epoch // 5 + 1, 5) by
         simulate(sums=True) -- j = 0 with simulate's own noise draw, j > 0 with es_randn_dev(seed + j) on
@@ -692,7 +693,19 @@ class MoEWrapper(nn.Module):
         half of every segment and scored on the second: c2st_auc / c2st_ks / c2st_acc / c2st_logloss / c2st_iter /
         c2st_converged (joint) and c2st_<name>_<e> (expert e; NaN where a half is empty on either side).  One
         further small copy; details=True adds c2st_obs_real / c2st_obs_gen [N, 10], c2st_theta and c2st_table.  The
-        values depend on N and on the order of the rows (see c2st).  The other keys keep their values bit for bit."""
+        values depend on N and on the order of the rows (see c2st).  The other keys keep their values bit for bit.
+
+        conditional=True adds the conditional profile of train.conditional.profile over the same ten observables
+        (the tables distances=True / classifier=True use, BEFORE normalise, computed once when several are on):
+        repetition 0 against the real rows, row i of both under the condition y_test[i, conditional_column], in
+        conditional_bins equally populated bins of that column, jointly and per (expert, bin) of the same expert
+        vector: cond_ws and, per observable name o of OBSERVABLE_NAMES, cond_ws_<o> / cond_bias_<o> / cond_width_<o>
+        / cond_ks_<o> (the count-weighted means over the bins of the Wasserstein distance, of the medians'
+        difference, of the widths' difference and of the KS statistic), and cond_ws_<e> / cond_ws_<o>_<e> over
+        expert e's bins (NaN where it has no row).  One further small copy; details=True adds cond_obs_real /
+        cond_obs_gen [N, 10] and the curves cond_edges, cond_count, cond_q_real, cond_q_gen, cond_mean_real,
+        cond_mean_gen, cond_std_real, cond_std_gen, cond_ws_bins, cond_ks_bins, cond_scale, cond_bin.  The other
+        keys keep their values bit for bit."""
         from ..train.utils import (FEATURE_NAMES, channel_sums, image_features, ws_across_experts_device,
                                    ws_feature_summary, ws_summary)
         dev = next(self.parameters()).device
@@ -729,7 +742,7 @@ class MoEWrapper(nn.Module):
                     expert = sim["expert"]
                 if (prdc or sliced) and j == 0:
                     gen_log = torch.log1p(sim["images"])
-                if (distances or classifier) and j == 0:
+                if (distances or classifier or conditional) and j == 0:
                     gen_feat0 = feat_gen[0] if features else image_features(sim["images"])[0]
             ws = ws_across_experts_device(sums_real, sums_gen, expert, E)
             if features:
@@ -758,7 +771,7 @@ class MoEWrapper(nn.Module):
             if details:
                 log.update(prdc_totals=raw["totals"], prdc_r_radius2=raw["r_radius2"],
                            prdc_f_radius2=raw["f_radius2"])
-        if distances or classifier:
+        if distances or classifier or conditional:
             from ..train import distances as dist
             with torch.cuda.device(dev):
                 raw_real = dist.observables(x, sums=sums_real, features=feat_real if features else None)
@@ -779,6 +792,19 @@ class MoEWrapper(nn.Module):
             log.update({k: v for k, v in c.items() if isinstance(v, float)})
             if details:
                 log.update(c2st_obs_real=raw_real, c2st_obs_gen=raw_gen, c2st_theta=c["theta"], c2st_table=c["table"])
+        if conditional:
+            from ..train import conditional as cnd
+            col = int(conditional_column)
+            if cond.dim() != 2 or not 0 <= col < cond.shape[1]:
+                raise ValueError(f"evaluate_device: conditional_column = {col} outside the {tuple(cond.shape)} conditions")
+            with torch.cuda.device(dev):
+                p = cnd.profile(raw_real, raw_gen, cond[:, col], int(conditional_bins), expert, E,
+                                names=dist.OBSERVABLE_NAMES, details=bool(details))    # one small D2H copy
+            log.update({k: v for k, v in p.items() if isinstance(v, float)})
+            if details:
+                log.update(cond_obs_real=raw_real, cond_obs_gen=raw_gen, cond_ws_bins=p["ws"], cond_ks_bins=p["ks"],
+                           **{f"cond_{k}": p[k] for k in ("edges", "count", "q_real", "q_gen", "mean_real", "mean_gen",
+                                                          "std_real", "std_gen", "scale", "bin")})
         if sliced:
             from ..train import sliced as swd
             with torch.cuda.device(dev):

@@ -128,7 +128,13 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     evaluate_device(classifier=True, classifier_degree=train.eval_classifier_degree) (train/classifier.py: c2st_auc,
     c2st_ks, c2st_acc, c2st_logloss, c2st_iter, c2st_converged, jointly and per expert), each key averaged over the
     batches in which it is finite; NaN if it is finite in none.  The classifier trains on the first half of a batch's
-    rows and is scored on the second, so the values depend on the batch size: compare runs at equal batch size."""
+    rows and is scored on the second, so the values depend on the batch size: compare runs at equal batch size.
+    train.eval_conditional (with eval_on_device only): also the conditional profile of
+    evaluate_device(conditional=True, conditional_bins=train.eval_conditional_bins,
+    conditional_column=train.eval_conditional_column) (train/conditional.py: cond_ws and per observable cond_ws_<o>,
+    cond_bias_<o>, cond_width_<o>, cond_ks_<o>, jointly and cond_ws_<e>, cond_ws_<o>_<e> per expert), each key averaged
+    over the batches in which it is finite; NaN if it is finite in none.  The bins are each batch's own quantiles of
+    the column: compare runs at equal batch size and equal train.eval_conditional_bins."""
     on_device = bool(cfg.train.get("eval_on_device", False))
     features = bool(cfg.train.get("eval_features", False))
     diagnostics = bool(cfg.train.get("eval_diagnostics", False))
@@ -140,6 +146,12 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
     sliced_proj = int(cfg.train.get("eval_sliced_proj", 256))
     classifier = bool(cfg.train.get("eval_classifier", False))
     classifier_degree = int(cfg.train.get("eval_classifier_degree", 2))
+    conditional = bool(cfg.train.get("eval_conditional", False))
+    conditional_bins = int(cfg.train.get("eval_conditional_bins", 8))
+    conditional_column = int(cfg.train.get("eval_conditional_column", 0))
+    if conditional and not on_device:
+        raise ValueError("train.eval_conditional needs train.eval_on_device: the conditional profiles exist on the "
+                         "device path only (MoEWrapper.evaluate_device)")
     if classifier and not on_device:
         raise ValueError("train.eval_classifier needs train.eval_on_device: the classifier two-sample test exists on "
                          "the device path only (MoEWrapper.evaluate_device)")
@@ -185,6 +197,10 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
         from .classifier import KEYS as C2ST_KEYS
         prdc_keys += list(C2ST_KEYS)
         prdc_keys += [f"{name}_{i}" for i in range(moe.n_experts) for name in C2ST_KEYS]
+    if conditional:
+        from .conditional import scalar_keys
+        from .distances import OBSERVABLE_NAMES
+        prdc_keys += scalar_keys(OBSERVABLE_NAMES, moe.n_experts)
     acc: Dict[str, List[float]] = {k: [] for k in keys + prdc_keys}
     seen = 0                                   # test samples in earlier batches
     conds = []                                 # the batches' device conditions (eval_diagnostics)
@@ -201,6 +217,9 @@ def evaluate_epoch(moe, test_loader, epoch: int, cfg, device, max_batches=None) 
                 extra.update(sliced=True, sliced_proj=sliced_proj)
             if classifier:
                 extra.update(classifier=True, classifier_degree=classifier_degree)
+            if conditional:
+                extra.update(conditional=True, conditional_bins=conditional_bins,
+                             conditional_column=conditional_column)
             m = moe.evaluate_device(epoch, cond_dev, real_images, cfg,
                                     seed=int(cfg.train.get("rng_seed", 1234)), sample_offset=seen,
                                     features=features, **extra)

@@ -1293,6 +1293,59 @@ int es_logit_scores(const void* real, int64_t r_ld, int r_rows, const int32_t* r
                     void* work, size_t work_bytes, es_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Conditional fidelity: order statistics per segment (csrc/quantile.hip) and rows to condition bins
+ * (csrc/bins.hip); the two rules are csrc/quantile_rule.h.
+ * ---------------------------------------------------------------------------------------- */
+/* es_segment_quantiles.  The arguments, the segment rule, the clamping, the caps, the limits and the workspace rule
+ * are es_wasserstein_1d's: u / v fp64 [rows][ld] (ld >= channels), DEVICE idx / seg, host u_cap / v_cap, one launch
+ * with each problem sorted in LDS while u_cap + v_cap <= ES_WS_LDS_MAX, global-memory passes over `work`
+ * (es_segment_quantiles_workspace bytes) up to 2^20, ES_ERR_ARG above that or with too small a workspace and nothing
+ * is launched.  Values must be finite.
+ * probs is the ONE HOST pointer of the call: n_q probabilities (1 <= n_q <= ES_QUANTILE_MAX_Q), copied into the
+ * launch arguments before the call returns; a probability outside [0, 1] or NaN gives ES_ERR_ARG before any launch.
+ * For column c of segment s, side 0 the u values and side 1 the v values, a side having n values
+ * x_(0) <= .. <= x_(n-1):
+ *   count[s * 2 + side] (int32) = n
+ *   out[((s * channels + c) * 2 + side) * n_q + k] (fp64) = the quantile at probs[k] by numpy's default rule:
+ *     h = probs[k] * (n - 1) (one fp64 multiplication), lo = floor(h), g = h - lo, hi = min(lo + 1, n - 1),
+ *     a = x_(lo), b = x_(hi), d = b - a, the result is g >= 0.5 ? b - d * (1 - g) : a + d * g,
+ *   every operation rounded on its own (no fused multiply-add): bit-equal to np.quantile(x, probs[k]).
+ * A side with n == 0 has NaN in all its n_q entries; the other side is still computed.  v == NULL with v_rows == 0
+ * and v_cap == 0 is the one-sample form (v_ld, v_idx, v_seg are not read; side 1 is empty everywhere).
+ * Both sides come out of ONE tagged sort of the problem (the sort of es_wasserstein_1d); the j-th order statistic
+ * of a side is the key at the position whose own tag is the side's and whose exclusive prefix count of that tag is
+ * j.  -0.0 and +0.0 are the same value and read as +0.0, so equal keys are equal values and the order the sort
+ * leaves inside a run cannot matter; no atomics; a rerun is bit-equal. */
+#define ES_QUANTILE_MAX_Q 16
+size_t es_segment_quantiles_workspace(int n_seg, int channels, int u_cap, int v_cap);
+int es_segment_quantiles(const double* u, int64_t u_ld, int u_rows, const int32_t* u_idx, const int32_t* u_seg,
+                         const double* v, int64_t v_ld, int v_rows, const int32_t* v_idx, const int32_t* v_seg,
+                         int n_seg, int channels, int u_cap, int v_cap, const double* probs /* HOST [n_q] */, int n_q,
+                         double* out /* [n_seg * channels, 2, n_q] */, int32_t* count /* [n_seg, 2] */, void* work,
+                         size_t work_bytes, es_stream_t stream);
+/* es_bin_dispatch.  x [rows] with element stride ld, fp32 or fp64 (x_f64 != 0; fp32 is widened exactly), finite;
+ * edges DEVICE fp64 [n_bins - 1], ascending, equal neighbours allowed (NULL when n_bins == 1); expert DEVICE int32
+ * [rows] or NULL (then n_experts must be 1).  1 <= n_bins <= ES_BINS_MAX, n_classes = n_bins * (expert ? n_experts
+ * : 1) <= 1024, 1 <= rows <= 2^20; outside that, with a NULL required pointer or too small a workspace: ES_ERR_ARG
+ * before any launch.
+ *   bin(x) = the number of edges strictly below x = np.searchsorted(edges, x, side="left"): the intervals are
+ *            pandas' (a, b], a value equal to an edge belongs to the lower bin;
+ *   class  = bin, or clamp(expert, 0, n_experts - 1) * n_bins + bin with an expert vector.
+ *   bin  (int32 [rows], may be NULL) = bin(x) of every row
+ *   perm (int32 [rows]), offs (int32 [n_classes + 1]) in es_router_dispatch's layout: the rows grouped by class,
+ *        each group in ascending row order, offs[c] the start of class c, offs[n_classes] = rows.
+ * The answer is np.argsort(class, kind="stable") and the cumulative counts, and it does not depend on the order
+ * in which anything lands: there is no atomic.  Three launches over chunks of 1024 rows -- per chunk a sort in LDS
+ * of (class, local row) that gives every row its rank inside its class and the chunk's class counts, one scan of
+ * the counts in (class, chunk) order, one scatter -- and no host synchronisation: every pointer is a device pointer.
+ * work: es_bin_dispatch_workspace(rows, n_classes) bytes (0: outside the limits). */
+#define ES_BINS_MAX 64
+size_t es_bin_dispatch_workspace(int rows, int n_classes);
+int es_bin_dispatch(const void* x, int x_f64, int64_t ld, int rows, const double* edges, int n_bins,
+                    const int32_t* expert, int n_experts, int32_t* bin /* [rows] or NULL */, int32_t* perm /* [rows] */,
+                    int32_t* offs /* [n_classes + 1] */, void* work, size_t work_bytes, es_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Simulation (inference) path: conditions in, calorimeter images out -- the reference's prediction
  * helpers (train/utils.py:179-266: generate, expm1, per-expert scatter into batch order) over the
  * eval-mode generators (neutron/generator.py:13-36 BatchNorm -> LeakyReLU chains).
